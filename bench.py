@@ -16,6 +16,13 @@ records are gathered to rank 0 with one RCCL gather after the timed region
 
 Prints ONE JSON line on rank 0.  ``value`` = landing control steps executed by
 all ranks / max-over-ranks wall time of the timed region.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints that line (the
+per-kernel times in it are the HIP events of the timed steps themselves).
+``--dump-outputs DIR`` also writes what the last timed step left (dump_outputs).
+``--full`` adds everything measured beside the headline: the CPU baseline, the RCCL
+gather check of a world of one, the QP status histogram and the single-GPU legs
+(``--no-cpu`` / ``--no-chol`` leave the CPU legs / the single-GPU legs out of it).
 """
 from __future__ import annotations
 
@@ -849,6 +856,27 @@ def structured_fitc_bench(ctx, reps=2):
             "note": "host-boundary times (H2D inputs, D2H results) around the device fit/predict"}
 
 
+def dump_outputs(fl, out_dir, rank=0):
+    """What the fleet holds after the last timed step, as ``out_dir/<name>.npy`` (float64,
+    about 1 KB per landing): ``records`` and ``x`` (Fleet.read: the per-landing records and
+    plant states), ``Xw`` / ``Uw`` / ``y`` / ``rho`` (Fleet.state: the plans the last QP
+    returned, shifted, and the ADMM's duals and step size) and ``post_mean`` / ``post_var``
+    (Fleet.posterior: the GP posterior the last step's QPs were built on; rows of landings
+    that flew no step then are written as 0).  Rank r > 0 of an N > 1 run writes
+    ``<name>_rank<r>.npy``.  The inputs are seeded, so equal arguments give equal inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = fl.state()
+    mean, var = fl.posterior()
+    arrays = {"records": st["rec"], "x": st["x"], "Xw": st["Xw"], "Uw": st["Uw"], "y": st["y"],
+              "rho": st["rho"], "post_mean": np.nan_to_num(mean, nan=0.0),
+              "post_var": np.nan_to_num(var, nan=0.0)}
+    # at most 64 MB in all: a larger fleet writes its first landings only
+    keep = max(1, int(60e6 // sum(8 * a[0].size for a in arrays.values())))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"),
+                np.ascontiguousarray(a[:keep], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -857,9 +885,14 @@ def main():
     ap.add_argument("--landings", type=int, default=1024, help="landings per GPU")
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--train", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline, the RCCL gather "
+                         "check of a world of one, the QP status histogram and the single-GPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-chol", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-chol", action="store_true", help="with --full: skip the single-GPU legs")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -867,7 +900,7 @@ def main():
     # the CPU baseline first: its worker processes start before this process
     # touches the GPU
     cb = None
-    if rank == 0 and world0 == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world0 == 1 and not args.no_cpu:
         cb = cpu_baseline(args.cpu_seconds, n_train=args.train, horizon=args.horizon)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -913,6 +946,8 @@ def main():
     admm_iters = float(np.sum(rec1[:, 11] - rec0[:, 11]))
     ph = np.array([[ev[k][i].elapsed_time(ev[k][i + 1]) for i in range(4)] for k in range(K)]) * 1e-3
     ph_mean = ph.mean(axis=0)
+    if args.dump_outputs:
+        dump_outputs(fl, args.dump_outputs, rank)
 
     # ---- aggregate over ranks (max time, summed work); one RCCL gather of records
     t = torch.tensor([el, steps_done, admm_iters], dtype=torch.float64, device="cuda")
@@ -926,10 +961,13 @@ def main():
     # records (a communicator of one at N = 1).  A set-up failure on any rank is agreed by
     # every rank and falls back to torch.distributed.gather together; `gather` records
     # which path ran and how many ranks RCCL's communicator spanned.
-    from gp_mpc_rocket_landing_amd.sharding import gather_shard_records
-    all_rec, gather_info = gather_shard_records(ctx, fl.records_dev, rec1, world * B, device="cuda")
-    if rank == 0 and world == 1 and gather_info["path"] == "rccl" and not np.array_equal(all_rec, rec1):
-        raise RuntimeError("RCCL gather of a world of one does not reproduce the fleet records")
+    # A world of one has its records already: its gather is a check, run with --full.
+    all_rec, gather_info = rec1, None
+    if world > 1 or args.full:
+        from gp_mpc_rocket_landing_amd.sharding import gather_shard_records
+        all_rec, gather_info = gather_shard_records(ctx, fl.records_dev, rec1, world * B, device="cuda")
+        if rank == 0 and world == 1 and gather_info["path"] == "rccl" and not np.array_equal(all_rec, rec1):
+            raise RuntimeError("RCCL gather of a world of one does not reproduce the fleet records")
 
     if rank == 0:
         P = B * args.horizon
@@ -1025,12 +1063,14 @@ def main():
             "admm_iters_per_solve": round(iters_all / max(steps_all, 1.0), 2),
             "landing_steps_per_gpu_step": round(steps_done / K, 1),
         }
-        out["gather"] = gather_info
+        if gather_info is not None:
+            out["gather"] = gather_info
         if all_rec is not None:
             oc = all_rec[:, 0]
             out["outcomes"] = {str(int(c)): int(np.sum(oc == c)) for c in np.unique(oc)}
-        out["qp_status"] = qp_status_histogram(fl)
-        if not args.no_chol and world == 1:  # single-GPU legs: the N > 1 runs keep to the metric
+        if args.full:
+            out["qp_status"] = qp_status_histogram(fl)
+        if args.full and not args.no_chol and world == 1:  # single-GPU legs: the N > 1 runs keep to the metric
             legs = [("single_landing", lambda: single_landing_bench(ctx, gp)),
                     ("surface_single_landing", lambda: surface_single_landing_bench(ctx)),
                     ("surface_gpmpc6", lambda: surface_gpmpc6_bench(ctx)),

@@ -28,7 +28,7 @@ run() {
   case $WL in
     main) timeout -k 10 300 python3 bench.py --no-cpu --no-chol --steps 20 --warmup 5 ;;
     full) echo "LOOP $(timeout -k 10 120 python3 scripts/probe.py gemm_loop | grep '^{')"
-          timeout -k 10 300 python3 bench.py --no-cpu --steps 20 ;;
+          timeout -k 10 300 python3 bench.py --full --no-cpu --steps 20 ;;
     chol) timeout -k 10 200 python3 scripts/probe.py chol ;;
     syrk_fitc) timeout -k 10 120 python3 scripts/probe.py syrk_fitc ;;
     rollouts6) timeout -k 10 300 python3 scripts/probe.py rollouts6 64,512 ;;

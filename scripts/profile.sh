@@ -5,7 +5,7 @@
 # Passes (each under its own time limit; --pmc passes alone, counters per the guide's limits):
 #   tests      the GPU suite (PYTEST_ARGS: extra pytest arguments, e.g. -k EXPR or test files)
 #   surface    the two drop-in surface legs (probe.py surface / surface6) -> surface.json, surface6.json
-#   bench      the default bench line -> bench.json
+#   bench      the full bench line (bench.py --full) -> bench.json
 #   trace      --kernel-trace --stats of the bench's main workload (--no-chol)
 #   fulltrace  the same over the full bench (every leg)
 #   fetch / write   --pmc FETCH_SIZE / WRITE_SIZE of the main workload -> pmc_traffic.json
@@ -38,12 +38,12 @@ for p in $PASSES; do
     surface) timeout -k 10 300 python3 scripts/probe.py surface > "$OUT/surface.json" 2>"$OUT/surface.err"
            timeout -k 10 300 python3 scripts/probe.py surface6 > "$OUT/surface6.json" 2>"$OUT/surface6.err"
            cat "$OUT/surface.json" "$OUT/surface6.json" ;;
-    bench) timeout -k 10 360 python3 bench.py > "$OUT/bench.log" 2>&1
+    bench) timeout -k 10 600 python3 bench.py --full > "$OUT/bench.log" 2>&1
            grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json" ;;
     trace) prof 300 trace --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
              python3 "$ROOT/bench.py" --no-cpu --no-chol ;;
     fulltrace) prof 560 fulltrace --kernel-trace --stats --output-format csv -d "$OUT/fulltrace" -o run -- \
-             python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu ;;
+             python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu ;;
     fetch) prof 300 fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- "${MAIN[@]}" ;;
     write) prof 300 write --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o run -- "${MAIN[@]}" ;;
     r6trace) prof 300 r6trace --kernel-trace --stats --output-format csv -d "$OUT/r6trace" -o run -- "${R6[@]}" ;;
