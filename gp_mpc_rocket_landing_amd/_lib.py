@@ -86,6 +86,12 @@ class FleetConfig(ctypes.Structure):
                 ("sqp_iters", ctypes.c_int), ("sqp_tol", ctypes.c_double), ("sqp_qp", QPSettings)]
 
 
+class FleetMCConfig(ctypes.Structure):
+    """gpmpc_fleet_mc_config: the Monte-Carlo protocol attachment of a fleet."""
+    _fields_ = [("thrust_dispersion", ctypes.c_double), ("aero_dispersion", ctypes.c_double),
+                ("log_steps", ctypes.c_int)]
+
+
 def _sig(name, res, *args):
     f = getattr(_L, name)
     f.restype = res
@@ -154,6 +160,9 @@ _sig("gpmpc_fleet_get_state", _c, _vp, _dp, _dp, _dp, _dp)
 _sig("gpmpc_fleet_get_posterior", _c, _vp, _dp, _dp)
 _sig("gpmpc_fleet_records_dev", _vp, _vp)
 _sig("gpmpc_fleet_destroy", _c, _vp)
+_sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
+_sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
+_sig("gpmpc_fleet_mc_detach", _c, _vp)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -191,7 +200,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_rollout6_get_state", "gpmpc_rollout6_destroy", "gpmpc_rollout6_create_exact",
             "gpmpc_rollout6_solve", "gpmpc_rollout6_solve_ref", "gpmpc_rollout6_set_state", "gpmpc_fitc_get_state",
             "gpmpc_rollout6_records_dev", "gpmpc_comm_unique_id", "gpmpc_comm_init", "gpmpc_comm_destroy",
-            "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit"]
+            "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
+            "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach"]
 
 
 class HIPError(RuntimeError):
@@ -557,6 +567,31 @@ def fleet_default_config(**kw):
         c.sqp_qp = c.qp
         set_fields(c.sqp_qp, sq)
     return c
+
+
+def fleet_mc_attach(h, max_steps, batch, thrust_dispersion=0.0, aero_dispersion=0.0, log=True, noise=None):
+    """gpmpc_fleet_mc_attach on the fleet handle ``h``: ``noise`` (batch, max_steps, 4)
+    standard normals or None; ``log``: keep the trajectories."""
+    cfg = FleetMCConfig(float(thrust_dispersion), float(aero_dispersion), int(max_steps) if log else 0)
+    nz = None
+    if noise is not None:
+        nz = f64(noise)
+        if nz.shape != (int(batch), int(max_steps), 4):
+            raise ValueError(f"noise must be (batch, max_steps, 4) = {(int(batch), int(max_steps), 4)}, got {nz.shape}")
+    _chk(_L.gpmpc_fleet_mc_attach(h, ctypes.byref(cfg), None if nz is None else _d(nz)), "fleet_mc_attach")
+
+
+def fleet_mc_read_log(h, max_steps, first, count):
+    """gpmpc_fleet_mc_read_log: (states (count, max_steps+1, 7), controls (count, max_steps, 3),
+    nsteps (count,)); rows past a landing's count are NaN."""
+    states = np.empty((count, max_steps + 1, 7)); controls = np.empty((count, max_steps, 3))
+    ns = np.zeros(count, np.int32)
+    _chk(_L.gpmpc_fleet_mc_read_log(h, int(first), int(count), _d(states), _d(controls), _i(ns)), "fleet_mc_read_log")
+    return states, controls, ns
+
+
+def fleet_mc_detach(h):
+    _chk(_L.gpmpc_fleet_mc_detach(h), "fleet_mc_detach")
 
 
 class QPWorkspace:

@@ -16,7 +16,10 @@
 //                        velocity rows of c_k with the correct sign (gp_mpc.py
 //                        :309-314, 410-411), the OSQP-style ADMM of
 //                        qp_device.h, the plant step (nominal Euler + the aero
-//                        residual the GP learns) and the warm-start shift.
+//                        residual the GP learns) and the warm-start shift;
+//   4. k_fleet_mc        only with the Monte-Carlo attachment (gpmpc_fleet_mc_attach):
+//                        the plant dispersions of monte_carlo.py:530-537 from a host
+//                        noise table and the step-major trajectory log (:539-544).
 #include "internal.h"
 #include "gemm.h"
 #include "qp.h"
@@ -76,6 +79,17 @@ struct gpmpc_fleet {
   gpmpc_fitc *fitc = nullptr;
   DevBuf part2;                              // |W2 k*|^2 partials
   int post_kind2 = 0, post_nrt2 = 0;
+  // Monte-Carlo protocol attachment (gpmpc_fleet_mc_attach; pooled on the context's
+  // stream): plant dispersions from a host-drawn noise table and the trajectory log
+  bool mc = false;
+  double mc_thrust = 0.0, mc_aero = 0.0;
+  int mc_log_steps = 0;                      // 0: no log, else cfg.max_steps
+  DevBuf mc_noise;                           // batch x max_steps x 4 standard normals (or empty)
+  DevBuf mc_u0;                              // batch x 3: the control kernel's applied control
+  DevBuf mc_cnt;                             // batch: appends so far (= the landing's steps)
+  DevBuf mc_mprev;                           // batch: mass at the last append (pre-step mass)
+  DevBuf mc_x0;                              // batch x 7: states[0] of every landing's log
+  DevBuf mc_logbuf;                          // step-major [t][landing][10]: x_{t+1}, u_t
 };
 
 // the GP the fleet reads: its exact GP, or the sparse one's inducing-point view
@@ -252,7 +266,11 @@ __device__ __forceinline__ void drag_residual(const double *x, double *d) {
 }
 
 __device__ __forceinline__ bool landing_ok(const double *x, double m0) {
-  // LandingConstraints.check_landing (monte_carlo.py:54-104), run_experiments.py tolerances
+  // LandingConstraints.check_landing (monte_carlo.py:54-104), run_experiments.py tolerances.
+  // Outcomes 1 and 4 both mean "landed" (the landing stops either way, monte_carlo.py
+  // :482-488); a caller with other LandingConstraints re-decides between them on the host
+  // from the record's final state (MonteCarloSimulator.run does, experiments/monte_carlo.py),
+  // so custom tolerances need no device change.
   if (fabs(x[1]) > 1.0) return false;
   if (fabs(x[2]) > 5.0 || fabs(x[3]) > 5.0) return false;
   if (fabs(x[4]) > 3.0) return false;
@@ -288,6 +306,7 @@ struct FleetArgs {
   int sqp, sqp_first, sqp_last;
   double sqp_tol;
   int *sqp_done;               // landing converged in an earlier pass of this control step
+  double *u0_out;              // batch x 3 applied controls of the plant step (or null: nothing attached)
 };
 
 // The latent variance of query row q from the SUMSQ partials (k_post_finish / k_fitc_finish
@@ -516,6 +535,7 @@ __global__ __launch_bounds__(256) void k_fleet_control(FleetArgs a) {
         const double u0[NU] = {s.x[NX], s.x[NX + 1], s.x[NX + 2]};
         double xn[NX], dr[3];
         plant_euler(sx, u0, dt, xn);
+        if (a.u0_out) for (int i = 0; i < NU; ++i) a.u0_out[(int64_t)b * NU + i] = u0[i];
         if (a.residual_model) {
           drag_residual(sx, dr);
           xn[4] += dr[0] * dt; xn[5] += dr[1] * dt; xn[6] += dr[2] * dt;
@@ -561,6 +581,7 @@ __global__ __launch_bounds__(256) void k_fleet_control(FleetArgs a) {
     }
     double xn[NX], dr[3];
     plant_euler(sx, u0, dt, xn);
+    if (a.u0_out) for (int i = 0; i < NU; ++i) a.u0_out[(int64_t)b * NU + i] = u0[i];
     if (a.residual_model) {
       drag_residual(sx, dr);
       xn[4] += dr[0] * dt; xn[5] += dr[1] * dt; xn[6] += dr[2] * dt;
@@ -856,6 +877,7 @@ __global__ __launch_bounds__(FQ_T) __attribute__((amdgpu_waves_per_eu(FQ_WPE, FQ
         const double u0[NU] = {s.rhs[NX], s.rhs[NX + 1], s.rhs[NX + 2]};
         double xn[NX], dr[3];
         plant_euler(sx, u0, dt, xn);
+        if (a.u0_out) for (int i = 0; i < NU; ++i) a.u0_out[(int64_t)b * NU + i] = u0[i];
         if (a.residual_model) {
           drag_residual(sx, dr);
           xn[4] += dr[0] * dt; xn[5] += dr[1] * dt; xn[6] += dr[2] * dt;
@@ -904,6 +926,7 @@ __global__ __launch_bounds__(FQ_T) __attribute__((amdgpu_waves_per_eu(FQ_WPE, FQ
     }
     double xn[NX], dr[3];
     plant_euler(sx, u0, dt, xn);
+    if (a.u0_out) for (int i = 0; i < NU; ++i) a.u0_out[(int64_t)b * NU + i] = u0[i];
     if (a.residual_model) {
       drag_residual(sx, dr);
       xn[4] += dr[0] * dt; xn[5] += dr[1] * dt; xn[6] += dr[2] * dt;
@@ -1060,6 +1083,208 @@ __global__ void k_fleet_reset(int first, int count, int N, int target_mode,
 }
 
 // ---------------------------------------------------------------------------
+// Monte-Carlo protocol attachment (gpmpc_fleet_mc_attach): MonteCarloSimulator.run_single's
+// plant dispersions (monte_carlo.py:530-537) and its trajectory lists (:539-544), after the
+// control kernel of every control step (in SQP mode after the last pass).
+//
+// A landing whose step count advanced in this step (rec[1] = its append count + 1; one that
+// terminated or diverged appends nothing: the break before the append, :455-544) gets
+//   v_next += (n0 thrust_dispersion) u0[0] / m_prev dt,  v_next += (n[1:4] aero_dispersion) dt
+// in the reference's order and roundings (no contraction), written to the plant state and
+// the record's state slots, and appends (x_{t+1}, u0_t) to the log at its own count t.
+//
+// One thread per landing does the arithmetic (a few flops) and stages its ten values in
+// LDS; the workgroup's 64 landings then append with consecutive threads on consecutive
+// doubles: the log is step-major, [t][landing][10], and landings reset together share t, so
+// one step's appends are one contiguous range of the fleet (640 doubles per workgroup)
+// instead of 80-byte pieces 2.4 KB x max_steps apart.  One small launch per control step.
+struct FleetMcArgs {
+  int B, max_steps, log;
+  double dt, thrust, aero;
+  const double *noise, *u0;
+  double *x, *rec, *mprev, *logbuf;
+  int *cnt;
+};
+#define MC_LPB 64   // landings per workgroup
+#define MC_ROW 10   // doubles per append: x (7), u0 (3)
+
+__global__ __launch_bounds__(256) void k_fleet_mc(FleetMcArgs a) {
+  __shared__ double sv[MC_LPB][MC_ROW];
+  __shared__ int st[MC_LPB];
+  const int tid = threadIdx.x, b0 = blockIdx.x * MC_LPB;
+  if (tid < MC_LPB) {
+    const int b = b0 + tid;
+    int t = -1;
+    if (b < a.B) {
+      double *rec = a.rec + (int64_t)b * GPMPC_REC_LEN;
+      const int c = a.cnt[b];
+      if ((int)rec[1] == c + 1 && c >= 0 && c < a.max_steps) {
+        t = c;
+        double xn[NX], u[NU];
+        for (int i = 0; i < NX; ++i) xn[i] = a.x[(int64_t)b * NX + i];
+        for (int i = 0; i < NU; ++i) u[i] = a.u0[(int64_t)b * NU + i];
+        if (a.thrust > 0.0 || a.aero > 0.0) {
+          const double *nz = a.noise + ((int64_t)b * a.max_steps + t) * 4;
+          if (a.thrust > 0.0) {  // thrust_noise * u[0] / x[0] * dt (monte_carlo.py:532-533)
+            const double d = __dmul_rn(__dmul_rn(__dmul_rn(nz[0], a.thrust), u[0]) / a.mprev[b], a.dt);
+            for (int i = 4; i < NX; ++i) xn[i] = __dadd_rn(xn[i], d);
+          }
+          if (a.aero > 0.0)      // aero_noise * dt (:536-537)
+            for (int i = 4; i < NX; ++i)
+              xn[i] = __dadd_rn(xn[i], __dmul_rn(__dmul_rn(nz[i - 3], a.aero), a.dt));
+          for (int i = 4; i < NX; ++i) {
+            a.x[(int64_t)b * NX + i] = xn[i];
+            rec[4 + i] = xn[i];
+          }
+        }
+        a.mprev[b] = xn[0];
+        a.cnt[b] = c + 1;
+        for (int i = 0; i < NX; ++i) sv[tid][i] = xn[i];
+        for (int i = 0; i < NU; ++i) sv[tid][NX + i] = u[i];
+      }
+    }
+    st[tid] = t;
+  }
+  __syncthreads();
+  if (!a.log) return;
+  for (int e = tid; e < MC_LPB * MC_ROW; e += blockDim.x) {
+    const int l = e / MC_ROW, j = e - l * MC_ROW, t = st[l];
+    if (t >= 0) a.logbuf[((int64_t)t * a.B + b0 + l) * MC_ROW + j] = sv[l][j];  // t < max_steps, b0 + l < B
+  }
+}
+
+// (re)start the logs of landings [first, first + count): no appends, states[0] = x0
+__global__ void k_fleet_mc_reset(int first, int count, const double *__restrict__ x0, int *cnt, double *mprev,
+                                 double *x0log) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int b = first + i;
+  cnt[b] = 0;
+  mprev[b] = x0[(int64_t)i * NX];
+  for (int c = 0; c < NX; ++c) x0log[(int64_t)b * NX + c] = x0[(int64_t)i * NX + c];
+}
+
+// attach to a fleet in flight: every landing's log starts at its current step and state
+__global__ void k_fleet_mc_init(int B, const double *__restrict__ rec, const double *__restrict__ x, int *cnt,
+                                double *mprev, double *x0log) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  cnt[b] = (int)rec[(int64_t)b * GPMPC_REC_LEN + 1];
+  mprev[b] = x[(int64_t)b * NX];
+  for (int c = 0; c < NX; ++c) x0log[(int64_t)b * NX + c] = x[(int64_t)b * NX + c];
+}
+
+static void fleet_mc_release(gpmpc_fleet *f) {
+  f->mc = false;
+  f->mc_thrust = f->mc_aero = 0.0;
+  f->mc_log_steps = 0;
+  f->mc_noise.release(); f->mc_u0.release(); f->mc_cnt.release(); f->mc_mprev.release();
+  f->mc_x0.release(); f->mc_logbuf.release();
+}
+
+extern "C" int gpmpc_fleet_mc_detach(gpmpc_fleet *f) {
+  GPMPC_CHECK_ARG(f);
+  if (!f->mc) return 0;
+  GPMPC_HIP(hipStreamSynchronize(f->ctx->stream));
+  fleet_mc_release(f);
+  return 0;
+}
+
+extern "C" int gpmpc_fleet_mc_attach(gpmpc_fleet *f, const gpmpc_fleet_mc_config *mc, const double *noise) {
+  GPMPC_CHECK_ARG(f && mc);
+  const int ms = f->cfg.max_steps;
+  if (!(mc->thrust_dispersion >= 0.0) || !(mc->aero_dispersion >= 0.0) || !std::isfinite(mc->thrust_dispersion) ||
+      !std::isfinite(mc->aero_dispersion)) {
+    gpmpc_set_error("fleet_mc_attach: the dispersions must be finite and >= 0");
+    return -2;
+  }
+  if (mc->log_steps != 0 && mc->log_steps != ms) {
+    gpmpc_set_error("fleet_mc_attach: log_steps must be 0 or the fleet's max_steps (%d), got %d", ms, mc->log_steps);
+    return -2;
+  }
+  const bool disp = mc->thrust_dispersion > 0.0 || mc->aero_dispersion > 0.0;
+  if (disp && !noise) {
+    gpmpc_set_error("fleet_mc_attach: a dispersion > 0 needs the noise table (batch x max_steps x 4)");
+    return -2;
+  }
+  if (ms < 1) {
+    gpmpc_set_error("fleet_mc_attach: the fleet's max_steps must be >= 1");
+    return -2;
+  }
+  GPMPC_HIP(hipSetDevice(f->ctx->device));
+  hipStream_t s = f->ctx->stream;
+  GPMPC_HIP(hipStreamSynchronize(s));
+  fleet_mc_release(f);
+  const size_t B = (size_t)f->B;
+  const size_t nlog = mc->log_steps ? (size_t)ms * B * MC_ROW : 0, nnoise = disp ? B * (size_t)ms * 4 : 0;
+  if (f->mc_u0.alloc(s, sizeof(double) * B * NU) || f->mc_cnt.alloc(s, sizeof(int) * B) ||
+      f->mc_mprev.alloc(s, sizeof(double) * B) || f->mc_x0.alloc(s, sizeof(double) * B * NX) ||
+      f->mc_logbuf.alloc(s, sizeof(double) * nlog) || f->mc_noise.alloc(s, sizeof(double) * nnoise)) {
+    fleet_mc_release(f);
+    gpmpc_set_error("fleet_mc_attach: out of device memory");
+    return -1;
+  }
+  GPMPC_HIP(hipMemsetAsync(f->mc_u0.p, 0, sizeof(double) * B * NU, s));
+  if (nlog) GPMPC_HIP(hipMemsetAsync(f->mc_logbuf.p, 0xff, sizeof(double) * nlog, s));  // all ones: NaN
+  if (nnoise) GPMPC_HIP(hipMemcpyAsync(f->mc_noise.p, noise, sizeof(double) * nnoise, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_fleet_mc_init, dim3((f->B + 255) / 256), dim3(256), 0, s, f->B, f->rec.as<double>(),
+                     f->x.as<double>(), f->mc_cnt.as<int>(), f->mc_mprev.as<double>(), f->mc_x0.as<double>());
+  GPMPC_HIP(hipGetLastError());
+  GPMPC_HIP(hipStreamSynchronize(s));  // the pageable noise table is the caller's again
+  f->mc_thrust = mc->thrust_dispersion;
+  f->mc_aero = mc->aero_dispersion;
+  f->mc_log_steps = mc->log_steps;
+  f->mc = true;
+  return 0;
+}
+
+extern "C" int gpmpc_fleet_mc_read_log(gpmpc_fleet *f, int first, int count, double *states, double *controls,
+                                       int *nsteps) {
+  GPMPC_CHECK_ARG(f && first >= 0 && count >= 0 && first + count <= f->B);
+  if (!f->mc || !f->mc_log_steps) {
+    gpmpc_set_error("fleet_mc_read_log: no trajectory log is attached (gpmpc_fleet_mc_attach with log_steps)");
+    return -2;
+  }
+  if (count == 0) return 0;
+  GPMPC_HIP(hipSetDevice(f->ctx->device));
+  hipStream_t s = f->ctx->stream;
+  const size_t C = (size_t)count, ms = (size_t)f->cfg.max_steps;
+  std::vector<int> cnt(C);
+  std::vector<double> x0(C * NX);
+  GPMPC_HIP(hipMemcpyAsync(cnt.data(), f->mc_cnt.as<int>() + first, sizeof(int) * C, hipMemcpyDeviceToHost, s));
+  GPMPC_HIP(hipMemcpyAsync(x0.data(), f->mc_x0.as<double>() + (size_t)first * NX, sizeof(double) * C * NX,
+                           hipMemcpyDeviceToHost, s));
+  GPMPC_HIP(hipStreamSynchronize(s));
+  size_t tmax = 0;
+  for (size_t i = 0; i < C; ++i) {
+    cnt[i] = std::min(std::max(cnt[i], 0), (int)ms);
+    tmax = std::max(tmax, (size_t)cnt[i]);
+  }
+  std::vector<double> rows(tmax * C * MC_ROW);  // [t][i][10]: the landings' columns of the first tmax steps
+  if (tmax) {
+    GPMPC_HIP(hipMemcpy2DAsync(rows.data(), sizeof(double) * C * MC_ROW,
+                               f->mc_logbuf.as<double>() + (size_t)first * MC_ROW, sizeof(double) * f->B * MC_ROW,
+                               sizeof(double) * C * MC_ROW, tmax, hipMemcpyDeviceToHost, s));
+    GPMPC_HIP(hipStreamSynchronize(s));
+  }
+  for (size_t i = 0; i < C; ++i) {
+    if (nsteps) nsteps[i] = cnt[i];
+    if (states) {
+      double *S = states + i * (ms + 1) * NX;
+      for (int c = 0; c < NX; ++c) S[c] = x0[i * NX + c];
+      for (size_t t = 0; t < ms; ++t)
+        for (int c = 0; c < NX; ++c)
+          S[(t + 1) * NX + c] = t < (size_t)cnt[i] ? rows[(t * C + i) * MC_ROW + c] : NAN;
+    }
+    if (controls) {
+      double *U = controls + i * ms * NU;
+      for (size_t t = 0; t < ms; ++t)
+        for (int c = 0; c < NU; ++c) U[t * NU + c] = t < (size_t)cnt[i] ? rows[(t * C + i) * MC_ROW + NX + c] : NAN;
+    }
+  }
+  return 0;
+}
+
 static int fleet_create(gpmpc_ctx *ctx, gpmpc_gp *gp, gpmpc_fitc *fitc, const gpmpc_fleet_config *cfg,
                         int batch, int fleet_batch, gpmpc_fleet **out) {
   GPMPC_CHECK_ARG(ctx && (gp || fitc) && cfg && out && batch > 0 && fleet_batch >= batch);
@@ -1210,6 +1435,11 @@ extern "C" int gpmpc_fleet_reset(gpmpc_fleet *f, int first, int count, const dou
                      f->Uw.as<double>(), f->ysc.as<double>(), f->m, f->rho.as<double>(),
                      f->cfg.qp.rho, f->rec.as<double>(), f->xt.as<double>());
   GPMPC_HIP(hipGetLastError());
+  if (f->mc) {  // restart those landings' logs: count 0, states[0] = x0
+    hipLaunchKernelGGL(k_fleet_mc_reset, dim3((count + 255) / 256), dim3(256), 0, s, first, count, d.as<double>(),
+                       f->mc_cnt.as<int>(), f->mc_mprev.as<double>(), f->mc_x0.as<double>());
+    GPMPC_HIP(hipGetLastError());
+  }
   GPMPC_HIP(hipStreamSynchronize(s));
   f->n_active = f->B;  // conservative until the host reads the records
   return 0;
@@ -1409,6 +1639,7 @@ static FleetArgs fleet_args(gpmpc_fleet *f) {
   a.sqp_last = f->sqp_it >= f->cfg.sqp_iters - 1;
   a.sqp_tol = f->cfg.sqp_tol;
   a.sqp_done = f->sqp_done.as<int>();
+  a.u0_out = f->mc ? f->mc_u0.as<double>() : nullptr;
   return a;
 }
 
@@ -1449,6 +1680,17 @@ extern "C" int gpmpc_fleet_step_phases(gpmpc_fleet *f, int phase_mask) {
       }
     }
     GPMPC_HIP(hipGetLastError());
+    // the attached Monte-Carlo protocol, once per control step: after the last SQP pass
+    if (f->mc && f->sqp_it >= (f->cfg.sqp_iters > 1 ? f->cfg.sqp_iters : 1) - 1) {
+      FleetMcArgs m;
+      m.B = f->B; m.max_steps = f->cfg.max_steps; m.log = f->mc_log_steps != 0;
+      m.dt = f->cfg.dt; m.thrust = f->mc_thrust; m.aero = f->mc_aero;
+      m.noise = f->mc_noise.as<double>(); m.u0 = f->mc_u0.as<double>();
+      m.x = f->x.as<double>(); m.rec = f->rec.as<double>(); m.mprev = f->mc_mprev.as<double>();
+      m.logbuf = f->mc_logbuf.as<double>(); m.cnt = f->mc_cnt.as<int>();
+      hipLaunchKernelGGL(k_fleet_mc, dim3((f->B + MC_LPB - 1) / MC_LPB), dim3(256), 0, f->ctx->stream, m);
+      GPMPC_HIP(hipGetLastError());
+    }
   }
   return 0;
 }
@@ -1547,6 +1789,7 @@ extern "C" double *gpmpc_fleet_records_dev(gpmpc_fleet *f) { return f ? f->rec.a
 
 extern "C" int gpmpc_fleet_destroy(gpmpc_fleet *f) {
   if (f && f->ctx) (void)hipStreamSynchronize(f->ctx->stream);
+  if (f) fleet_mc_release(f);  // the attachment's pooled buffers go back to the context's pool
   delete f;
   return 0;
 }

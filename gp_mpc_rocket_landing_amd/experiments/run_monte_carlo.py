@@ -11,6 +11,10 @@ ADMM, plant and the MonteCarloSimulator termination rules all device-resident
 -- then the 16-double records are gathered to rank 0 with one collective and
 summarised like MonteCarloSimulator's statistics (monte_carlo.py:186-272).
 
+``--trajectories OUT.npz`` (one GPU, 3-DoF) attaches the fleet's trajectory log and saves
+every landing's states (landings, max_steps+1, 7), controls (landings, max_steps, 3) and
+step counts (rows past a landing's count are NaN) beside the records.
+
 ``--six-dof`` runs BASELINE configs[4] instead: 6-DoF GP-MPC rollouts (N = 30,
 the StructuredRocketGP FITC pair at M = 2000 / N = 4000, every rank fitting it
 deterministically), default 512 rollouts sharded the same way:
@@ -54,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--train", type=int, default=None, help="GP training rows, default 1000 (4000 with --six-dof)")
     ap.add_argument("--seed0", type=int, default=42)
     ap.add_argument("--out", default="")
+    ap.add_argument("--trajectories", default="", metavar="OUT.npz",
+                    help="single GPU, 3-DoF: log and save every landing's states and controls")
     ap.add_argument("--six-dof", action="store_true", help="BASELINE configs[4]: 6-DoF rollouts")
     ap.add_argument("--inducing", type=int, default=2000, help="--six-dof: FITC inducing points")
     args = ap.parse_args(argv)
@@ -71,6 +77,8 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.trajectories and (world > 1 or args.six_dof):
+        ap.error("--trajectories needs a single-GPU 3-DoF run (the log is not gathered across ranks)")
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
@@ -87,6 +95,8 @@ def main(argv=None):
         # landing's record is bit-identical to the unsharded run's
         fl = Fleet(ctx, gp, max(count, 1), fleet_batch=max(args.landings, 1), max_steps=args.max_steps)
         x0 = initial_conditions(count, args.seed0, first) if count else None
+        if args.trajectories:
+            fl.attach_mc(log=True)
     t0 = time.perf_counter()
     rec = np.zeros((0, _lib.REC_LEN))
     if count:
@@ -117,6 +127,9 @@ def main(argv=None):
         print(json.dumps(s), flush=True)
         if args.out:
             np.savez(args.out, records=allrec)
+        if args.trajectories and count:
+            states, controls, nsteps = fl.read_log()
+            np.savez_compressed(args.trajectories, records=allrec, states=states, controls=controls, nsteps=nsteps)
     fl.close()
     if world > 1:
         dist.barrier()

@@ -107,6 +107,24 @@ class Fleet:
                   "fleet_get_posterior")
         return mean, var
 
+    def attach_mc(self, thrust_dispersion=0.0, aero_dispersion=0.0, log=True, noise=None):
+        """The Monte-Carlo protocol of MonteCarloSimulator.run_single around the control
+        step (gpmpc_fleet_mc_attach): plant dispersions from ``noise`` (batch, max_steps,
+        4) standard normals -- column 0 the thrust draw, 1..3 the aero draws; None when
+        both dispersions are 0 -- and, with ``log``, the trajectories ``read_log`` returns."""
+        _lib.fleet_mc_attach(self.h, int(self.cfg.max_steps), self.batch, thrust_dispersion, aero_dispersion,
+                             log, noise)
+
+    def read_log(self, first=0, count=None):
+        """(states (count, max_steps+1, 7), controls (count, max_steps, 3), nsteps (count,))
+        of landings [first, first+count): states[0] is the state at the reset, row t+1 and
+        controls row t the t-th control step; rows past nsteps are NaN."""
+        count = self.batch - int(first) if count is None else int(count)
+        return _lib.fleet_mc_read_log(self.h, int(self.cfg.max_steps), int(first), count)
+
+    def detach_mc(self):
+        _lib.fleet_mc_detach(self.h)
+
     @property
     def records_dev(self):
         return _lib._L.gpmpc_fleet_records_dev(self.h)

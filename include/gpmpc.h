@@ -325,6 +325,43 @@ int gpmpc_fleet_set_stamps(gpmpc_fleet *f, void *dev_u64x16);
  * uint64 device buffer; NULL disables): start and end s_memrealtime (100 MHz),
  * HW_ID and XCC_ID of the landing's first wave */
 int gpmpc_fleet_set_trace(gpmpc_fleet *f, void *dev_u64xbx4);
+/* ---- Monte-Carlo protocol attachment (optional; entry points only, ABI 4 unchanged) --
+ * What MonteCarloSimulator.run_single does around the control step besides the
+ * termination rules: the plant dispersions (monte_carlo.py:530-537) and the trajectory
+ * lists of SimulationResult (:539-544).  With nothing attached the fleet launches exactly
+ * what it launches without these entry points; attached, one more small kernel follows
+ * the control kernel of every control step (in SQP mode: of the last pass), and for each
+ * landing whose step count advanced in that step
+ *   v_next += (n0 thrust_dispersion) u0[0] / m_prev dt   (thrust_dispersion > 0; m_prev the
+ *                                                          pre-step mass, u0[0] the first
+ *                                                          control component only, :533)
+ *   v_next += (n[1:4] aero_dispersion) dt                 (aero_dispersion > 0)
+ * in that order and with the reference's roundings, written to the plant state and the
+ * record's state slots, then (x_{t+1}, u0_t) is appended to the landing's log.  A landing
+ * that terminates or diverges in a step appends nothing (the break before the append).
+ * Landing outcomes 1 and 4 are both "landed" with the compiled run_experiments.py
+ * tolerances; a caller with its own LandingConstraints re-decides between them on the host
+ * from the record's final state. */
+typedef struct {
+  double thrust_dispersion; /* SimulationConfig.thrust_dispersion (>= 0) */
+  double aero_dispersion;   /* SimulationConfig.aero_dispersion (>= 0) */
+  int log_steps;            /* 0: no trajectory log; else the fleet's max_steps */
+} gpmpc_fleet_mc_config;
+/* noise: host, batch x max_steps x 4 standard normals, row [landing][step]: column 0 the
+ * thrust draw, 1..3 the aero draws (copied; NULL allowed when both dispersions are 0).
+ * Buffers come from the context's pool.  Attaching to landings in flight starts each log
+ * at the landing's current step and state.  Replaces an earlier attachment.  -2: bad
+ * arguments (a dispersion > 0 without noise, a negative dispersion, log_steps neither 0
+ * nor max_steps). */
+int gpmpc_fleet_mc_attach(gpmpc_fleet *f, const gpmpc_fleet_mc_config *mc, const double *noise);
+/* the logs of landings [first, first+count): states (count x (max_steps+1) x 7, row 0 the
+ * state at the reset), controls (count x max_steps x 3: the applied u0 of every step),
+ * nsteps (count: appends so far = the landing's control steps); any may be NULL.  Rows
+ * past a landing's count are NaN.  -2 without an attached log. */
+int gpmpc_fleet_mc_read_log(gpmpc_fleet *f, int first, int count, double *states, double *controls, int *nsteps);
+/* drop the attachment (gpmpc_fleet_destroy does too); gpmpc_fleet_reset restarts the
+ * reset landings' logs (count 0, states[0] = x0) and leaves the others' alone */
+int gpmpc_fleet_mc_detach(gpmpc_fleet *f);
 /* ---- uncertainty propagation (uncertainty_prop.py:117-177) ------------------
  * Replaces the covariance recursion of UncertaintyPropagator._propagate_linear
  * (Sigma_next = A_d @ Sigma_k @ A_d.T + Q_gp, uncertainty_prop.py:163-167) for
