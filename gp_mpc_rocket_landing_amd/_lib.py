@@ -159,6 +159,7 @@ _sig("gpmpc_gram_grad", _c, _vp, _c, _dp, _c, _dp, _c, _c, _dp, ctypes.c_double,
 _sig("gpmpc_fleet_get_state", _c, _vp, _dp, _dp, _dp, _dp)
 _sig("gpmpc_fleet_get_posterior", _c, _vp, _dp, _dp)
 _sig("gpmpc_fleet_records_dev", _vp, _vp)
+_sig("gpmpc_fleet_query_launches", _c, _vp)
 _sig("gpmpc_fleet_destroy", _c, _vp)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
@@ -201,7 +202,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_rollout6_solve", "gpmpc_rollout6_solve_ref", "gpmpc_rollout6_set_state", "gpmpc_fitc_get_state",
             "gpmpc_rollout6_records_dev", "gpmpc_comm_unique_id", "gpmpc_comm_init", "gpmpc_comm_destroy",
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
-            "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach"]
+            "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
+            "gpmpc_fleet_query_launches"]
 
 
 class HIPError(RuntimeError):

@@ -4,7 +4,8 @@
 //   1. k_fleet_queries   Simple3DoF features (features.py:403-444) of the N
 //                        horizon points of b's linearisation trajectory
 //                        (X_lin, U_lin = shifted previous solution: RTI), scaled
-//                        by the kernel lengthscales;
+//                        by the kernel lengthscales (fleet_query_row; at fleet sizes the
+//                        row-tiled gram kernel forms them itself and this launch is skipped);
 //   2. GP posterior      K* = k(Z*, X) (gram kernel), mean = K* alpha and
 //                        var = sigma2 - |L^-1 K*^T|^2 on the FP64-MFMA GEMM with
 //                        fused sum-of-squares epilogue (gemm.hip) -- all B*N
@@ -66,6 +67,7 @@ struct gpmpc_fleet {
   bool fuse_post = true;                     // GPMPC_FLEET_FUSE_POST=0: separate k_post_finish
   int64_t post_P = 0;                        // query rows / partial row tiles of the last
   int post_nrt = 0;                          //   posterior GEMM (fused finish reads them)
+  int query_launches = 0;                    // k_fleet_queries launches so far (diagnostic)
   // Every size-dependent path choice is made once, at creation, for plan_B landings (the
   // fleet's own size, or the whole Monte-Carlo fleet this one is a shard of): the kernels
   // differ in summation order, so choosing them from the running count or the shard size
@@ -147,19 +149,6 @@ static void mpc_pattern(int N, std::vector<int> &rp, std::vector<int> &ci) {
 }
 
 #endif  // FLEET_WIDE_TU
-__device__ __forceinline__ void features3(const double *x, const double *u, double *z) {
-  // Simple3DoFFeatureExtractor.extract (features.py:403-444)
-  const double vx = x[4], vy = x[5], vz = x[6], alt = x[1];
-  const double speed = sqrt(vx * vx + vy * vy + vz * vz);
-  const double rho = 1.225 * exp(-alt / 8500.0);
-  const double qd = 0.5 * rho * speed * speed;
-  const double tm = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-  z[0] = vx / 10.0; z[1] = vy / 10.0; z[2] = vz / 10.0; z[3] = speed / 10.0;
-  z[4] = qd / (0.5 * 1.225 * 100.0);
-  z[5] = u[0] / 10.0; z[6] = u[1] / 10.0; z[7] = u[2] / 10.0; z[8] = tm / 10.0;
-  z[9] = alt / 100.0; z[10] = rho / 1.225;
-}
-
 // GPMPC.solve's loop: X_pred[0] = x0 (gp_mpc.py:263) -- before the first pass of
 // a control step the unshifted plan's first point becomes the current state
 #ifndef FLEET_WIDE_TU
@@ -178,18 +167,10 @@ __global__ void k_fleet_queries(int B, int N, const double *__restrict__ Xw,
                                 double *__restrict__ Qn) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;  // = slot*N + k
   if (g >= B * N) return;
-  const int sl = g / N, k = g - sl * N;
-  const int b = order ? order[sl] : sl;
-  double z[NFEAT];
-  features3(Xw + ((int64_t)b * (N + 1) + k) * NX, Uw + ((int64_t)b * N + k) * NU, z);
-  double s = 0.0;
+  double v[NFEAT];
+  Qn[g] = fleet_query_row(FleetPlans{Xw, Uw, ls, order, N, iso}, g, v);
 #pragma unroll
-  for (int f = 0; f < NFEAT; ++f) {
-    const double v = iso ? z[f] : z[f] / ls[f];
-    Q[(int64_t)g * NFEAT + f] = v;
-    s += v * v;
-  }
-  Qn[g] = s;
+  for (int f = 0; f < NFEAT; ++f) Q[(int64_t)g * NFEAT + f] = v[f];
 }
 
 // The queries and K* in one launch for a fleet of at most 64 query rows (one to three
@@ -207,18 +188,10 @@ __global__ __launch_bounds__(256) void k_fleet_queries_gram(int B, int N, const 
   __shared__ double sqn[64];
   const int P = B * N, tid = threadIdx.x;
   if (tid < P) {
-    const int sl = tid / N, k = tid - sl * N;
-    const int b = order ? order[sl] : sl;
-    double z[NFEAT];
-    features3(Xw + ((int64_t)b * (N + 1) + k) * NX, Uw + ((int64_t)b * N + k) * NU, z);
-    double sn = 0.0;
+    double v[NFEAT];
+    sqn[tid] = fleet_query_row(FleetPlans{Xw, Uw, ls, order, N, iso}, tid, v);
 #pragma unroll
-    for (int f = 0; f < NFEAT; ++f) {
-      const double v = iso ? z[f] : z[f] / ls[f];
-      sq[tid][f] = v;
-      sn += v * v;
-    }
-    sqn[tid] = sn;
+    for (int f = 0; f < NFEAT; ++f) sq[tid][f] = v[f];
   }
   __syncthreads();
   const int col = blockIdx.x * 64 + (tid & 63), rg = tid >> 6;
@@ -1475,13 +1448,24 @@ static hipError_t fleet_gp_posterior(gpmpc_fleet *f, int mask) {
                        g.kind, g.Xs, g.Xn, g.n, g.sigma2, g.iso_scale, f->Ks.as<double>());
     if ((e = hipGetLastError()) != hipSuccess) return e;
   } else if (mask & 1) {
-    hipLaunchKernelGGL(k_fleet_queries, dim3((P + 255) / 256), dim3(256), 0, s, nb, f->N,
-                       f->Xw.as<double>(), f->Uw.as<double>(), g.ls, g.kind == GPMPC_SE_ISO,
-                       f->use_order ? f->order.as<int>() : nullptr, f->Q.as<double>(),
-                       f->Qn.as<double>());
+    // GPMPC_GRAM_FEAT=0: the query rows from a launch of their own (k_fleet_queries -> Q).
+    // Default: the row-tiled Gram kernel forms its 128 rows itself (same function, same
+    // bits), one launch and the Q round trip less; Q is then not written.
+    static const bool feat_env = [] {
+      const char *v = getenv("GPMPC_GRAM_FEAT");
+      return !v || atoi(v) != 0;
+    }();
+    const FleetPlans pl{f->Xw.as<double>(), f->Uw.as<double>(), g.ls, f->use_order ? f->order.as<int>() : nullptr,
+                        f->N, g.kind == GPMPC_SE_ISO};
+    const bool in_gram = feat_env && !fused && !cs && g.d == NFEAT && gram_rows_tiled(P, g.d);
+    if (!in_gram) {
+      hipLaunchKernelGGL(k_fleet_queries, dim3((P + 255) / 256), dim3(256), 0, s, nb, f->N, pl.Xw, pl.Uw, pl.ls,
+                         pl.iso, pl.order, f->Q.as<double>(), f->Qn.as<double>());
+      ++f->query_launches;
+    }
     if (!fused && !cs) {
       e = launch_gram(s, g.kind, f->Q.as<double>(), f->Qn.as<double>(), P, g.Xs, g.Xn, g.n, g.d,
-                      g.sigma2, g.iso_scale, f->Ks.as<double>(), g.n, 0);
+                      g.sigma2, g.iso_scale, f->Ks.as<double>(), g.n, 0, in_gram ? &pl : nullptr);
       if (e != hipSuccess) return e;
     }
   }
@@ -1784,6 +1768,8 @@ extern "C" int gpmpc_fleet_get_posterior(gpmpc_fleet *f, double *mean, double *v
       }
   return 0;
 }
+
+extern "C" int gpmpc_fleet_query_launches(gpmpc_fleet *f) { return f ? f->query_launches : -1; }
 
 extern "C" double *gpmpc_fleet_records_dev(gpmpc_fleet *f) { return f ? f->rec.as<double>() : nullptr; }
 

@@ -86,6 +86,9 @@ __global__ __launch_bounds__(256) void k_gram(int kind, const double *__restrict
 // Row-major K (no transpose), compile-time kernel kind and width: 64 columns x
 // 128 rows per workgroup (each thread one column, 32 rows, 8 independent
 // exponentials in flight), same arithmetic as k_gram (identical bits).
+// plans (D = 11 only; Xw null: none): the a-rows are a fleet's query rows and the
+// workgroup forms its 128 from the landings' plans (fleet_query_row) instead of
+// reading a / na.
 #ifndef GRAM_ROWS
 #define GRAM_ROWS 128
 #endif
@@ -101,16 +104,31 @@ __global__ __launch_bounds__(256) void k_gram_rows(const double *__restrict__ a,
                                                    const double *__restrict__ b,
                                                    const double *__restrict__ nb, int n2,
                                                    double sigma2, double iso_scale,
-                                                   double *__restrict__ K, int64_t ldk) {
+                                                   double *__restrict__ K, int64_t ldk,
+                                                   FleetPlans plans) {
   __shared__ double sa[GRAM_ROWS][D + 1];
   __shared__ double sna[GRAM_ROWS];
   const int r0 = blockIdx.y * GRAM_ROWS, c0 = blockIdx.x * GRAM_TILE;
   const int tid = threadIdx.x;
-  for (int e = tid; e < GRAM_ROWS * D; e += 256) {
-    const int r = e / D, k = e - r * D;
-    sa[r][k] = (r0 + r < n1) ? a[(int64_t)(r0 + r) * D + k] : 0.0;
+  if (D == 11 && plans.Xw) {
+    // the a-rows are the fleet's query rows: formed here (one thread per row, every column
+    // tile again) instead of read back from a features launch
+    if (tid < GRAM_ROWS) {
+      double v[11], sn = 0.0;
+#pragma unroll
+      for (int k = 0; k < 11; ++k) v[k] = 0.0;
+      if (r0 + tid < n1) sn = fleet_query_row(plans, r0 + tid, v);
+#pragma unroll
+      for (int k = 0; k < 11; ++k) sa[tid][k] = v[k];
+      sna[tid] = sn;
+    }
+  } else {
+    for (int e = tid; e < GRAM_ROWS * D; e += 256) {
+      const int r = e / D, k = e - r * D;
+      sa[r][k] = (r0 + r < n1) ? a[(int64_t)(r0 + r) * D + k] : 0.0;
+    }
+    if (tid < GRAM_ROWS) sna[tid] = (r0 + tid < n1) ? na[r0 + tid] : 0.0;
   }
-  if (tid < GRAM_ROWS) sna[tid] = (r0 + tid < n1) ? na[r0 + tid] : 0.0;
   const int col = c0 + (tid & 63);
   constexpr int RPT = GRAM_ROWS / 4;  // rows per thread
   const int rb = (tid >> 6) * RPT;
@@ -155,41 +173,50 @@ __global__ __launch_bounds__(256) void k_gram_rows(const double *__restrict__ a,
 template <int D>
 static hipError_t launch_gram_rows(hipStream_t s, int kind, const double *a, const double *na,
                                    int n1, const double *b, const double *nb, int n2,
-                                   double sigma2, double iso_scale, double *K, int64_t ldk) {
+                                   double sigma2, double iso_scale, double *K, int64_t ldk,
+                                   const FleetPlans *plans) {
+  const FleetPlans pl = plans ? *plans : FleetPlans{};
   dim3 g((n2 + GRAM_TILE - 1) / GRAM_TILE, (n1 + GRAM_ROWS - 1) / GRAM_ROWS);
   switch (kind) {
     case GPMPC_SE_ARD:
       hipLaunchKernelGGL((k_gram_rows<D, GPMPC_SE_ARD>), g, dim3(256), 0, s, a, na, n1, b, nb, n2,
-                         sigma2, iso_scale, K, ldk);
+                         sigma2, iso_scale, K, ldk, pl);
       break;
     case GPMPC_SE_ISO:
       hipLaunchKernelGGL((k_gram_rows<D, GPMPC_SE_ISO>), g, dim3(256), 0, s, a, na, n1, b, nb, n2,
-                         sigma2, iso_scale, K, ldk);
+                         sigma2, iso_scale, K, ldk, pl);
       break;
     case GPMPC_MATERN32:
       hipLaunchKernelGGL((k_gram_rows<D, GPMPC_MATERN32>), g, dim3(256), 0, s, a, na, n1, b, nb,
-                         n2, sigma2, iso_scale, K, ldk);
+                         n2, sigma2, iso_scale, K, ldk, pl);
       break;
     default:
       hipLaunchKernelGGL((k_gram_rows<D, GPMPC_MATERN52>), g, dim3(256), 0, s, a, na, n1, b, nb,
-                         n2, sigma2, iso_scale, K, ldk);
+                         n2, sigma2, iso_scale, K, ldk, pl);
   }
   return hipGetLastError();
 }
 
-hipError_t launch_gram(hipStream_t s, int kind, const double *a, const double *na, int n1,
-                       const double *b, const double *nb, int n2, int d, double sigma2,
-                       double iso_scale, double *K, int64_t ldk, int transpose_out) {
-  if (n1 <= 0 || n2 <= 0) return hipSuccess;
-  if (d > GRAM_MAXD) return hipErrorInvalidValue;
+bool gram_rows_tiled(int n1, int d) {
   static const int rows_env = [] {
     const char *v = getenv("GPMPC_GRAM_ROWS");
     return v ? atoi(v) : 1;
   }();
-  if (rows_env && !transpose_out && n1 >= 4 * GRAM_ROWS) {
-    if (d == 11) return launch_gram_rows<11>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk);
-    if (d == 12) return launch_gram_rows<12>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk);
-    if (d == 13) return launch_gram_rows<13>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk);
+  return rows_env && n1 >= 4 * GRAM_ROWS && d >= 11 && d <= 13;
+}
+
+hipError_t launch_gram(hipStream_t s, int kind, const double *a, const double *na, int n1,
+                       const double *b, const double *nb, int n2, int d, double sigma2,
+                       double iso_scale, double *K, int64_t ldk, int transpose_out,
+                       const FleetPlans *plans) {
+  if (n1 <= 0 || n2 <= 0) return hipSuccess;
+  if (d > GRAM_MAXD) return hipErrorInvalidValue;
+  const bool rows = !transpose_out && gram_rows_tiled(n1, d);
+  if (plans && !(rows && d == 11)) return hipErrorInvalidValue;  // only k_gram_rows<11> forms the rows
+  if (rows) {
+    if (d == 11) return launch_gram_rows<11>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk, plans);
+    if (d == 12) return launch_gram_rows<12>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk, nullptr);
+    return launch_gram_rows<13>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk, nullptr);
   }
   dim3 g((n2 + GRAM_TILE - 1) / GRAM_TILE, (n1 + GRAM_TILE - 1) / GRAM_TILE);
   switch (d) {

@@ -188,12 +188,56 @@ __device__ __forceinline__ double kernel_epilogue(int kind, double d2, double si
   }
 }
 
+// Simple3DoFFeatureExtractor.extract (features.py:403-444)
+__device__ __forceinline__ void features3(const double *x, const double *u, double *z) {
+  const double vx = x[4], vy = x[5], vz = x[6], alt = x[1];
+  const double speed = sqrt(vx * vx + vy * vy + vz * vz);
+  const double rho = 1.225 * exp(-alt / 8500.0);
+  const double qd = 0.5 * rho * speed * speed;
+  const double tm = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  z[0] = vx / 10.0; z[1] = vy / 10.0; z[2] = vz / 10.0; z[3] = speed / 10.0;
+  z[4] = qd / (0.5 * 1.225 * 100.0);
+  z[5] = u[0] / 10.0; z[6] = u[1] / 10.0; z[7] = u[2] / 10.0; z[8] = tm / 10.0;
+  z[9] = alt / 100.0; z[10] = rho / 1.225;
+}
+
+// The linearisation plans of a 3-DoF fleet (fleet.hip), for kernels that form the GP
+// query rows themselves: row g = slot * N + k is horizon point k of landing order[slot]
+// (or of landing slot without a dispatch order).  Xw null: no plans.
+struct FleetPlans {
+  const double *Xw, *Uw, *ls;
+  const int *order;
+  int N, iso;
+};
+
+// Query row g of the plans: its 11 features over the lengthscales into v, the squared
+// norm returned.  The one place this arithmetic lives, so every kernel that forms the
+// rows (k_fleet_queries, k_fleet_queries_gram, k_gram_rows) produces the same bits.
+__device__ __forceinline__ double fleet_query_row(const FleetPlans &p, int g, double *v) {
+  const int sl = g / p.N, k = g - sl * p.N;
+  const int b = p.order ? p.order[sl] : sl;
+  double z[11];
+  features3(p.Xw + ((int64_t)b * (p.N + 1) + k) * 7, p.Uw + ((int64_t)b * p.N + k) * 3, z);
+  double s = 0.0;
+#pragma unroll
+  for (int f = 0; f < 11; ++f) {
+    v[f] = p.iso ? z[f] : z[f] / p.ls[f];
+    s += v[f] * v[f];
+  }
+  return s;
+}
+
 // ---- internal device entry points shared across translation units ----------
 // Gram: K (n1 x n2, ldk) from pre-scaled rows (a = X1/ls, b = X2/ls) and their
-// squared norms; kind selects the epilogue.
+// squared norms; kind selects the epilogue.  With plans (row-tiled kernel only, see
+// gram_rows_tiled) the a-rows are the fleet's query rows, formed in the kernel: a and na
+// are not read.
 hipError_t launch_gram(hipStream_t s, int kind, const double *a, const double *na, int n1,
                        const double *b, const double *nb, int n2, int d, double sigma2,
-                       double iso_scale, double *K, int64_t ldk, int transpose_out);
+                       double iso_scale, double *K, int64_t ldk, int transpose_out,
+                       const FleetPlans *plans = nullptr);
+// launch_gram takes the row-tiled kernel (k_gram_rows) for this shape, row-major output
+bool gram_rows_tiled(int n1, int d);
 #define GPMPC_KPROG 16  // GpCore kind of a composite-kernel program
 // composite kernel programs (gram.hip; codes GPMPC_KP_* in gpmpc.h): Gram of raw rows,
 // same = 1: one row set (X2 ignored; WhiteNoise on the diagonal)

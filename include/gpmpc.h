@@ -313,6 +313,9 @@ int gpmpc_fleet_get_state(gpmpc_fleet *f, double *Xw, double *Uw, double *y_scal
  * those read the posterior at their own trajectory, landings past it read NaN.
  * -2 when use_gp = 0. */
 int gpmpc_fleet_get_posterior(gpmpc_fleet *f, double *mean, double *var);
+/* diagnostic: launches of the query-feature kernel (k_fleet_queries) since the fleet was
+ * created; a step whose Gram kernel forms the query rows itself adds none.  -1: f NULL */
+int gpmpc_fleet_query_launches(gpmpc_fleet *f);
 /* diagnostic: accumulate s_memtime cycles of landing 0's control kernel per
  * phase into dev_u64x16 (16 x uint64 device buffer; NULL disables):
  * 0 assembly, 1 scaling, 2 factor, 3 A' rhs, 4 KKT solve (band path, or the
