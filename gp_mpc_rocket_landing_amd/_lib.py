@@ -161,6 +161,9 @@ _sig("gpmpc_fleet_get_posterior", _c, _vp, _dp, _dp)
 _sig("gpmpc_fleet_records_dev", _vp, _vp)
 _sig("gpmpc_fleet_query_launches", _c, _vp)
 _sig("gpmpc_fleet_destroy", _c, _vp)
+_i64 = ctypes.c_int64
+_sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64,
+     ctypes.c_double, ctypes.c_double, _c, _c, _c, _ip)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
 _sig("gpmpc_fleet_mc_detach", _c, _vp)
@@ -203,7 +206,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_rollout6_records_dev", "gpmpc_comm_unique_id", "gpmpc_comm_init", "gpmpc_comm_destroy",
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
-            "gpmpc_fleet_query_launches"]
+            "gpmpc_fleet_query_launches", "gpmpc_gemm_diag"]
 
 
 class HIPError(RuntimeError):
@@ -705,3 +708,124 @@ def cov_propagate(ctx, A, q, S0=None, s0_diag=1e-6):
     _chk(_L.gpmpc_cov_propagate(ctx.h, B, N, nx, _d(A), _d(q), s0, float(s0_diag), _d(out)),
          "cov_propagate")
     return out
+
+
+# ---- diagnostic: the internal GEMM launchers (gpmpc_gemm_diag) -----------------
+GEMM_OP = {"nt": 0, "nn": 1, "nn_batched": 2, "tn": 3, "rowblock": 4, "lat0": 5, "lat1": 6, "syrk_diag": 7,
+           "updsolve": 8, "sumsq": 9, "sumsq_mean": 10}
+GEMM_TRI_A, GEMM_LOWER_C, GEMM_TRI_B = 1, 2, 4
+GEMM_PATH = {-1: "none", 0: "64", 1: "128", 2: "128_ksplit", 3: "streamk", 4: "splitk", 5: "lat", 6: "syrk_diag",
+             7: "updsolve"}
+GEMM_GRID = {0: "2d", 1: "tri", 2: "xcd_batch", 3: "rowblock_xcd"}
+GEMM_SUMSQ_64, GEMM_SUMSQ_128, GEMM_SUMSQ_SPLITK = 0, 1, 2
+
+
+class GemmOperand:
+    """Where an operand of gemm_diag lies inside a flat float64 device tensor: ``batch``
+    matrices of ``rows`` x ``cols`` elements, leading dimension ``ld``, ``stride`` elements
+    apart, the first at element ``offset``."""
+
+    def __init__(self, tensor, offset, rows, cols, ld, stride=0, batch=1):
+        self.tensor, self.offset, self.rows, self.cols = tensor, int(offset), int(rows), int(cols)
+        self.ld, self.stride, self.batch = int(ld), int(stride), int(batch)
+
+    def last(self):
+        """The furthest element the description reaches (offset - 1 when it is empty)."""
+        if self.rows <= 0 or self.cols <= 0 or self.batch <= 0:
+            return self.offset - 1
+        return self.offset + (self.batch - 1) * self.stride + (self.rows - 1) * self.ld + self.cols - 1
+
+    def check(self, name, rows, cols, batch):
+        import torch
+        t = self.tensor
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1
+                and t.is_contiguous()):
+            raise ValueError(f"gemm_diag: operand {name} needs a flat contiguous float64 device tensor")
+        if self.rows < rows or self.cols < cols or self.batch != batch:
+            raise ValueError(f"gemm_diag: operand {name} is described as {self.batch} x {self.rows} x {self.cols}, "
+                             f"the operation touches {batch} x {rows} x {cols}")
+        if self.ld < self.cols or self.stride < 0 or self.offset < 0:
+            raise ValueError(f"gemm_diag: operand {name}: ld {self.ld} < cols {self.cols}, or a negative "
+                             "stride / offset")
+        if self.last() >= t.numel():
+            raise ValueError(f"gemm_diag: operand {name} reaches element {self.last()} of a tensor of {t.numel()}")
+
+    def ptr(self):
+        return self.tensor.data_ptr() + 8 * self.offset
+
+
+def gemm_sumsq_rows(kind, M):
+    """Rows of the SUMSQ partial buffer under a forced kind (csrc/gemm.h gemm_sumsq_rows)."""
+    return (M + 127) // 128 if kind == GEMM_SUMSQ_128 else (M + 63) // 64
+
+
+def _gemm_extents(op, M, N, K, p0, p1):
+    """(rows, cols) every operand of the operation touches (None: unused)."""
+    o = GEMM_OP
+    if op in (o["nt"], o["rowblock"], o["lat0"]):
+        return {"A": (M, K), "B": (N, K), "C": (M, N), "D": None}
+    if op in (o["nn"], o["nn_batched"]):
+        return {"A": (M, K), "B": (K, N), "C": (M, N), "D": None}
+    if op == o["tn"]:
+        return {"A": (K, M), "B": (K, N), "C": (M, N), "D": None}
+    if op in (o["lat1"], o["syrk_diag"]):
+        return {"A": (M, K), "B": None, "C": (M, M), "D": None}
+    if op == o["updsolve"]:
+        return {"A": (M, K) if (K > 0 or p0 > 0) else None, "B": (128, K) if K > 0 else None,
+                "C": (M, 128 + p0), "D": (128, 128)}
+    if op in (o["sumsq"], o["sumsq_mean"]):
+        n_out = p1 if op == o["sumsq_mean"] else 0
+        rows = gemm_sumsq_rows(p0, M + n_out) if p0 >= 0 else (M + n_out + 63) // 64
+        return {"A": (M + n_out, M), "B": (N, M), "C": (rows, N), "D": (n_out, N) if n_out else None}
+    raise ValueError(f"gemm_diag: unknown op {op}")
+
+
+def gemm_diag(ctx, op, M, N, K, A=None, B=None, C=None, D=None, alpha=1.0, beta=0.0, flags=0, p0=0, p1=0,
+              batch=1):
+    """One internal GEMM launcher on device tensors (gpmpc_gemm_diag; tests only).  ``op`` is
+    a GEMM_OP name; A, B, C, D are GemmOperand descriptions (None where the operation takes
+    no such operand).  Raises ValueError, before anything is launched, when a description
+    is smaller than what the operation touches or reaches past its tensor; HIPError (rc -2)
+    when the library refuses the combination.  Returns (path, split, grid) as the names of
+    GEMM_PATH / GEMM_GRID and the split count.  The launch is asynchronous on ctx's stream."""
+    opc = GEMM_OP[op] if isinstance(op, str) else int(op)
+    M, N, K, batch, p0, p1 = int(M), int(N), int(K), int(batch), int(p0), int(p1)
+    if min(M, N, K) < 0 or batch < 1:
+        raise ValueError("gemm_diag: negative dimension or batch < 1")
+    ext = _gemm_extents(opc, M, N, K, p0, p1)
+    ops = {"A": A, "B": B, "C": C, "D": D}
+    for name, d in ops.items():
+        if ext[name] is None:
+            continue
+        if d is None:
+            raise ValueError(f"gemm_diag: operand {name} missing")
+        d.check(name, ext[name][0], ext[name][1], batch)
+
+    def g(d, f):
+        return f(d) if d is not None else 0
+
+    if opc == GEMM_OP["updsolve"]:
+        # Linv is 128 x 128 at ld 128; its batch stride travels as ldd.  B shares A's stride.
+        if D.ld != 128:
+            raise ValueError("gemm_diag: updsolve's Linv has ld 128")
+        if A is not None and B is not None and (B.ld != A.ld or B.stride != A.stride):
+            raise ValueError("gemm_diag: updsolve's B shares A's ld and stride")
+        if C.ld != (A.ld if A is not None else C.ld):
+            raise ValueError("gemm_diag: updsolve's C shares A's ld")
+        ldd = D.stride
+        lda = C.ld
+    else:
+        ldd = g(D, lambda d: d.ld)
+        lda = g(A, lambda d: d.ld)
+    if opc in (GEMM_OP["sumsq"], GEMM_OP["sumsq_mean"]) and (A.ld != M or B.ld != M):
+        raise ValueError("gemm_diag: the SUMSQ operands are packed (ld n)")
+    if opc == GEMM_OP["syrk_diag"] and (C.ld != A.ld or C.stride != A.stride):
+        raise ValueError("gemm_diag: syrk_diag's C shares A's ld and stride")
+    path = np.full(3, -9, np.int32)
+    rc = _L.gpmpc_gemm_diag(ctx.h, opc, M, N, K, batch, g(A, GemmOperand.ptr) or None, lda,
+                            g(A, lambda d: d.stride), g(B, GemmOperand.ptr) or None, g(B, lambda d: d.ld),
+                            g(B, lambda d: d.stride), g(C, GemmOperand.ptr) or None, g(C, lambda d: d.ld),
+                            g(C, lambda d: d.stride), g(D, GemmOperand.ptr) or None, ldd, float(alpha),
+                            float(beta), int(flags), p0, p1, _i(path))
+    _chk(rc, "gemm_diag")
+    return GEMM_PATH[int(path[0])], int(path[1]), GEMM_GRID[int(path[2])]

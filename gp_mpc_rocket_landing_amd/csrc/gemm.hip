@@ -20,6 +20,19 @@
 
 #define GT 64
 #define GK 16
+
+// The kernel path, K split and grid mapping of this thread's last launch_* call, recorded
+// where the kernel is launched (gpmpc_gemm_diag reports them; the values are
+// GPMPC_GEMM_PATH_* / GPMPC_GEMM_GRID_* of gpmpc.h).
+enum { PATH_NONE = -1, PATH_64 = 0, PATH_128 = 1, PATH_128_KSPLIT = 2, PATH_STREAMK = 3, PATH_SPLITK = 4,
+       PATH_LAT = 5, PATH_SYRK_DIAG = 6, PATH_UPDSOLVE = 7 };
+enum { GRID_2D = 0, GRID_TRI = 1, GRID_XCD_BATCH = 2, GRID_ROWBLOCK_XCD = 3 };
+static thread_local int g_path[3] = {PATH_NONE, 0, 0};
+static inline void gemm_path(int path, int split = 1, int grid = GRID_2D) {
+  g_path[0] = path;
+  g_path[1] = split;
+  g_path[2] = grid;
+}
 #define GP 18
 static_assert(GK * (GT + 2) <= GT * GP, "k-major B tile must fit the row-major B buffer");
 
@@ -479,6 +492,7 @@ hipError_t launch_syrk128_diag(hipStream_t s, int w, int K, const double *A, int
   if (w <= 0 || K <= 0 || batch <= 0) return hipSuccess;
   if (w > BT) return hipErrorInvalidValue;
   if (ks < 1) ks = 1;
+  gemm_path(PATH_SYRK_DIAG, ks);
   hipLaunchKernelGGL(k_syrk128_diag, dim3(batch * ks), dim3(256), 0, s, w, K, A, lda, C, stride, ks);
   return hipGetLastError();
 }
@@ -572,6 +586,7 @@ hipError_t launch_gemm_updsolve(hipStream_t s, int M, int K, const double *A, in
   if (M <= 0) return hipSuccess;
   if (batch % 8 || wn > BT || wn > M) return hipErrorInvalidValue;
   const dim3 g(1, (M + BT - 1) / BT, batch);
+  gemm_path(PATH_UPDSOLVE, 1, GRID_ROWBLOCK_XCD);
   if (K == 0 && wn == 0)
     hipLaunchKernelGGL((k_gemm128_updsolve<false, true>), g, dim3(256), 0, s, M, K, A, lda, B, C, Linv, sA, sC, sL,
                        0);
@@ -903,6 +918,7 @@ hipError_t launch_gemm_lat(hipStream_t s, int mode, int M, int N, int K, const d
                            int64_t sC) {
   if (M <= 0 || N <= 0 || batch <= 0) return hipSuccess;
   if (K > 8 * LAT_CH || (mode == 0 && N > 128) || (mode == 1 && N != M)) return hipErrorInvalidValue;
+  gemm_path(PATH_LAT, 1, mode == 0 ? GRID_2D : GRID_TRI);
   if (mode == 0) {
     hipLaunchKernelGGL(k_gemm_lat<0>, dim3((M + 15) / 16, 1, batch), dim3(256), 0, s, M, N, K, A,
                        lda, B, ldb, C, ldc, alpha, beta, tri_b, sA, sB, sC);
@@ -960,6 +976,7 @@ static bool launch_splitk(hipStream_t s, int form, int M, int N, int K, const do
   const int64_t sA = form == 2 ? (int64_t)kc * lda : kc, sB = form == 0 ? kc : (int64_t)kc * ldb;
   const int klast = K - (S - 1) * kc;  // the last chunk's length (one launch for all chunks)
   const dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, S);
+  gemm_path(PATH_SPLITK, S);
   if (form == 0)
     hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 0, 0>), g, dim3(256), 0, s, M, N, kc, A, lda, B, ldb, P, (int64_t)N,
                        1.0, 0.0, 0, 0, sA, sB, MN, M, nullptr, (int64_t)0, 0, 0, klast);
@@ -1022,6 +1039,7 @@ static bool launch_splitk_sumsq(hipStream_t s, int M, int N, int K, const double
   const int64_t MN = (int64_t)M * N;
   double *P = (double *)gpmpc_scratch(s, 5, sizeof(double) * MN * S);
   if (!P) return false;
+  gemm_path(PATH_SPLITK, S);
   hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 0, 0>), dim3(1, ty, S), dim3(256), 0, s, M, N, kc, A, lda, B, ldb, P,
                      (int64_t)N, 1.0, 0.0, 0, 0, (int64_t)kc, (int64_t)kc, MN, M, nullptr, (int64_t)0, 0, 0,
                      K - (S - 1) * kc);
@@ -1092,6 +1110,7 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
     const int T = tg ? ty * (ty + 1) / 2 : tx * ty;
     const int64_t total = (int64_t)T * batch * ((K + GK - 1) / GK);
     const int nwg = (int)std::min<int64_t>(512, total);
+    gemm_path(PATH_STREAMK, nwg, tg ? GRID_TRI : GRID_2D);
     hipLaunchKernelGGL(k_gemm128_sk, dim3(nwg), dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
                        alpha, (int)tg, tx, T, sA, sB, sC, total);
     return hipGetLastError();
@@ -1123,6 +1142,7 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
     // 1-D order that interleaves them over the 8 XCDs (a 2-D grid whose
     // column count is a multiple of 8 pins columns to XCDs: 8x imbalance)
     dim3 g(tg ? ty * (ty + 1) / 2 : tx, tg ? 1 : ty, batch * ksplit);
+    gemm_path(ksplit > 1 ? PATH_128_KSPLIT : PATH_128, ksplit, tg ? GRID_TRI : GRID_2D);
     if (epi == EPI_STORE)
       hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
                          alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, ksplit,
@@ -1157,6 +1177,7 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
   dim3 g = xb ? dim3(T * ((batch + 7) / 8) * 8, 1, 1)
          : tg ? dim3(T, 1, batch) : remap ? dim3(tx * ty, 1, 1) : dim3(tx, ty, batch);
   const int rt = tg ? -1 : remap ? ty : 0;
+  gemm_path(PATH_64, 1, xb ? GRID_XCD_BATCH : tg ? GRID_TRI : GRID_2D);
   if (epi == EPI_STORE)
     hipLaunchKernelGGL(k_gemm_nt<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
                        alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, rt, xb, 0);
@@ -1174,6 +1195,7 @@ hipError_t launch_gemm_nn(hipStream_t s, int M, int N, int K, const double *A, i
   hipError_t e = hipSuccess;
   if (launch_splitk(s, 1, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
   dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, 1);
+  gemm_path(PATH_64);
   hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 0>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
                      ldc, alpha, beta, 0, 0, (int64_t)0, (int64_t)0, (int64_t)0, M, nullptr,
                      (int64_t)0, 0, 0, 0);
@@ -1186,6 +1208,7 @@ hipError_t launch_gemm_nn_batched(hipStream_t s, int M, int N, int K, const doub
                                   double alpha, double beta, int batch) {
   if (M <= 0 || N <= 0 || batch <= 0) return hipSuccess;
   dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, batch);
+  gemm_path(PATH_64);
   hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 0>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
                      ldc, alpha, beta, 0, 0, sA, sB, sC, M, nullptr, (int64_t)0, 0, 0, 0);
   return hipGetLastError();
@@ -1199,6 +1222,7 @@ hipError_t launch_gemm_tn(hipStream_t s, int M, int N, int K, const double *A, i
   hipError_t e = hipSuccess;
   if (launch_splitk(s, 2, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
   dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, 1);
+  gemm_path(PATH_64);
   hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 1>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
                      ldc, alpha, beta, 0, 0, (int64_t)0, (int64_t)0, (int64_t)0, M, nullptr,
                      (int64_t)0, 0, 0, 0);
@@ -1223,6 +1247,7 @@ hipError_t launch_gemm_nt_rowblock(hipStream_t s, int M, int N, int K, const dou
     return e ? atoi(e) : 1;
   }();
   const int tg = (xb_env && batch >= 8 && batch % 8 == 0) ? 3 : 0;
+  gemm_path(ksplit > 1 ? PATH_128_KSPLIT : PATH_128, ksplit, tg ? GRID_ROWBLOCK_XCD : GRID_2D);
   hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
                      alpha, beta, 0, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, ksplit, tg);
   return hipGetLastError();
@@ -1247,4 +1272,89 @@ hipError_t launch_gemm_sumsq_mean(hipStream_t s, int n, int n_out, int P, const 
                                   int64_t ldm, int kind) {
   return launch_gemm_impl(s, EPI_SUMSQ, n + n_out, P, n, Wext, n, Ks, n, part, ldp, 1.0, 0.0, 1, 0,
                           1, 0, 0, 0, n, meanT, ldm, kind);
+}
+
+// ---------------------------------------------------------------------------
+// Diagnostic: one internal launcher, called with the caller's arguments on the context's
+// stream, so that tests reach every kernel of this file directly (the product reaches
+// them only through the potrf, the TRSM and the GP fits / predicts).  op picks the
+// launcher (GPMPC_GEMM_OP_*, gpmpc.h); arguments outside that launcher's contract
+// (gemm.h) are refused with -2 and nothing is launched.  The extents of the device
+// buffers cannot be checked here: the caller answers for them.  path[0..2]: the kernel
+// path, its K split (chunks / workgroups of the split forms) and the grid mapping the
+// launcher took, PATH_NONE when it launched nothing (an empty product).
+extern "C" int gpmpc_gemm_diag(gpmpc_ctx *ctx, int op, int M, int N, int K, int batch, const double *A,
+                               int64_t lda, int64_t sA, const double *B, int64_t ldb, int64_t sB, double *C,
+                               int64_t ldc, int64_t sC, double *D, int64_t ldd, double alpha, double beta,
+                               int flags, int p0, int p1, int *path) {
+  GPMPC_CHECK_ARG(ctx && path && M >= 0 && N >= 0 && K >= 0 && batch >= 1);
+  GPMPC_CHECK_ARG((flags & ~7) == 0);
+  const int tri_a = flags & 1, lower_c = (flags >> 1) & 1, tri_b = (flags >> 2) & 1;
+  hipStream_t s = ctx->stream;
+  gemm_path(PATH_NONE, 0);
+  hipError_t e = hipSuccess;
+  switch (op) {
+    case 0:  // launch_gemm_nt, EPI_STORE
+      GPMPC_CHECK_ARG(A && B && C && lda >= K && ldb >= K && ldc >= N && !tri_b);
+      // a triangular A is never accumulated into C (the K split is cut for a full A)
+      GPMPC_CHECK_ARG(!tri_a || (beta != 1.0 && K <= M));
+      e = launch_gemm_nt(s, EPI_STORE, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, tri_a, lower_c, batch, sA,
+                         sB, sC);
+      break;
+    case 1:  // launch_gemm_nn
+      GPMPC_CHECK_ARG(A && B && C && lda >= K && ldb >= N && ldc >= N && batch == 1 && !flags);
+      e = launch_gemm_nn(s, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta);
+      break;
+    case 2:  // launch_gemm_nn_batched
+      GPMPC_CHECK_ARG(A && B && C && lda >= K && ldb >= N && ldc >= N && !flags);
+      e = launch_gemm_nn_batched(s, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta, batch);
+      break;
+    case 3:  // launch_gemm_tn
+      GPMPC_CHECK_ARG(A && B && C && lda >= M && ldb >= N && ldc >= N && batch == 1 && !flags);
+      e = launch_gemm_tn(s, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta);
+      break;
+    case 4:  // launch_gemm_nt_rowblock, p0 = ksplit
+      GPMPC_CHECK_ARG(A && B && C && lda >= K && ldb >= K && ldc >= N && N <= BT && !tri_a && !tri_b);
+      GPMPC_CHECK_ARG(p0 >= 1 && (p0 == 1 || beta == 1.0));
+      e = launch_gemm_nt_rowblock(s, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, batch, sA, sB, sC, lower_c, p0);
+      break;
+    case 5:  // launch_gemm_lat, mode 0
+      GPMPC_CHECK_ARG(A && B && C && lda >= K && ldb >= K && ldc >= N && N <= 128 && K <= 8 * LAT_CH && !tri_a &&
+                      !lower_c);
+      e = launch_gemm_lat(s, 0, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, tri_b, batch, sA, sB, sC);
+      break;
+    case 6:  // launch_gemm_lat, mode 1 (B = A: the launcher ignores B, ldb, sB)
+      GPMPC_CHECK_ARG(A && C && lda >= K && ldc >= N && M == N && K <= 8 * LAT_CH && !flags);
+      e = launch_gemm_lat(s, 1, M, N, K, A, lda, nullptr, lda, C, ldc, alpha, beta, 0, batch, sA, sA, sC);
+      break;
+    case 7:  // launch_syrk128_diag: w = M, p0 = ks; C (ld lda) and A share the batch stride sA
+      GPMPC_CHECK_ARG(A && C && M <= BT && lda >= K && lda >= M && p0 >= 1 && !flags);
+      e = launch_syrk128_diag(s, M, K, A, lda, C, batch, sA, p0);
+      break;
+    case 8:  // launch_gemm_updsolve: Linv = D (stride ldd), p0 = wn; B shares A's stride
+      GPMPC_CHECK_ARG(C && D && batch % 8 == 0 && p0 >= 0 && p0 <= BT && p0 <= M && lda >= K + BT && !flags);
+      GPMPC_CHECK_ARG(K == 0 || (A && B));
+      // the look-ahead reads A's rows over K + 128 columns and writes D = C + 128: C is A's next columns
+      GPMPC_CHECK_ARG(p0 == 0 || (A && C == A + K && lda >= (int64_t)K + BT + p0 && sC == sA));
+      e = launch_gemm_updsolve(s, M, K, A, lda, B, C, D, batch, sA, sC, ldd, p0);
+      break;
+    case 9:  // launch_gemm_sumsq: n = M = K, P = N, Ks = B, part = C, p0 = kind
+      GPMPC_CHECK_ARG(A && B && C && K == M && ldc >= N && batch == 1 && p0 >= -1 && p0 <= GEMM_SUMSQ_SPLITK &&
+                      !flags);
+      e = launch_gemm_sumsq(s, M, N, A, B, C, ldc, p0);
+      break;
+    case 10:  // launch_gemm_sumsq_mean: the same with Wext = A, p1 = n_out, meanT = D (ld ldd)
+      GPMPC_CHECK_ARG(A && B && C && K == M && ldc >= N && batch == 1 && p0 >= -1 && p0 <= GEMM_SUMSQ_SPLITK &&
+                      !flags);
+      GPMPC_CHECK_ARG(p1 >= 0 && (p1 == 0 || (D && ldd >= N)));
+      e = launch_gemm_sumsq_mean(s, M, p1, N, A, B, C, ldc, D, ldd, p0);
+      break;
+    default:
+      GPMPC_CHECK_ARG(op >= 0 && op <= 10);
+  }
+  GPMPC_HIP(e);
+  path[0] = g_path[0];
+  path[1] = g_path[1];
+  path[2] = g_path[2];
+  return 0;
 }

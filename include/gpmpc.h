@@ -114,6 +114,44 @@ int gpmpc_syrk_batched_dev(gpmpc_ctx *ctx, int n, int k, int batch, const double
 int gpmpc_trsm_lower(gpmpc_ctx *ctx, int n, int nrhs, const double *L, int ldl, double *B, int ldb);
 /* Replaces scipy.linalg.cho_solve((L, True), B) (exact_gp.py:179; sparse_gp.py:210,214). */
 int gpmpc_potrs(gpmpc_ctx *ctx, int n, int nrhs, const double *L, int ldl, double *B, int ldb);
+/* diagnostic (tests only; no product path calls it): one launcher of the internal FP64
+ * MFMA GEMM family (csrc/gemm.h) on device pointers, so that every kernel of the family
+ * can be compared with an exact reference.  All matrices row-major, batch members
+ * sA / sB / sC elements apart.  Per op (unused arguments are ignored):
+ *   NT          C = alpha A (M x K) B (N x K)^T + beta C; flags TRI_A (A lower triangular,
+ *               K <= M, beta != 1), LOWER_C (only C[i][j], j <= i, is written)
+ *   NN / NN_BATCHED  B is K x N;   TN  A is K x M, B is K x N  (NN, TN: batch 1)
+ *   ROWBLOCK    the NT product with N <= 128 (C may alias A); LOWER_C, p0 = K split
+ *               (> 1 only with beta = 1)
+ *   LAT0        the NT product with N <= 128, K <= 128 (C may alias A); TRI_B
+ *   LAT1        lower C = alpha A A^T + beta C, M = N, K <= 128 (B unused)
+ *   SYRK_DIAG   lower C (M x M, M <= 128, ld lda, stride sA) -= A (M x K) A^T, p0 = K split
+ *   UPDSOLVE    C (M x 128, ld lda) <- (C - A (M x K) B (128 x K)^T) Linv^T, Linv = D
+ *               (128 x 128 lower, stride ldd), batch a multiple of 8, B at stride sA;
+ *               p0 = wn (<= 128, <= M; > 0 needs C = A + K): also the lower wn x wn block
+ *               at C + 128 -= A[0:wn, 0:K+128] A[0:wn, 0:K+128]^T
+ *   SUMSQ       A (n x n lower, ld n; n = M = K), Ks = B (P x n, ld n; P = N): part = C
+ *               (ld ldc), row t = the column sums of squares of (A Ks^T) over row tile t;
+ *               p0 = forced kind (-1 the launcher's choice, 0 64-row tiles, 1 128-row
+ *               tiles, 2 the K split, which keeps 64-row tiles)
+ *   SUMSQ_MEAN  the same with A = [W; alpha^T] ((n + p1) x n): rows n.. of the product go
+ *               to D (p1 x P, ld ldd)
+ * A combination outside the launcher's contract returns -2 and launches nothing; the
+ * caller answers for the extents of its buffers.  path[0] = the kernel path taken
+ * (GPMPC_GEMM_PATH_*, -1 when the product is empty), path[1] = its K split (chunks of the
+ * split forms, workgroups of stream-K; 1 otherwise), path[2] = the grid mapping. */
+enum { GPMPC_GEMM_OP_NT = 0, GPMPC_GEMM_OP_NN = 1, GPMPC_GEMM_OP_NN_BATCHED = 2, GPMPC_GEMM_OP_TN = 3,
+       GPMPC_GEMM_OP_ROWBLOCK = 4, GPMPC_GEMM_OP_LAT0 = 5, GPMPC_GEMM_OP_LAT1 = 6, GPMPC_GEMM_OP_SYRK_DIAG = 7,
+       GPMPC_GEMM_OP_UPDSOLVE = 8, GPMPC_GEMM_OP_SUMSQ = 9, GPMPC_GEMM_OP_SUMSQ_MEAN = 10 };
+enum { GPMPC_GEMM_TRI_A = 1, GPMPC_GEMM_LOWER_C = 2, GPMPC_GEMM_TRI_B = 4 };
+enum { GPMPC_GEMM_PATH_64 = 0, GPMPC_GEMM_PATH_128 = 1, GPMPC_GEMM_PATH_128_KSPLIT = 2,
+       GPMPC_GEMM_PATH_STREAMK = 3, GPMPC_GEMM_PATH_SPLITK = 4, GPMPC_GEMM_PATH_LAT = 5,
+       GPMPC_GEMM_PATH_SYRK_DIAG = 6, GPMPC_GEMM_PATH_UPDSOLVE = 7 };
+enum { GPMPC_GEMM_GRID_2D = 0, GPMPC_GEMM_GRID_TRI = 1, GPMPC_GEMM_GRID_XCD_BATCH = 2,
+       GPMPC_GEMM_GRID_ROWBLOCK_XCD = 3 };
+int gpmpc_gemm_diag(gpmpc_ctx *ctx, int op, int M, int N, int K, int batch, const double *A, int64_t lda,
+                    int64_t sA, const double *B, int64_t ldb, int64_t sB, double *C, int64_t ldc, int64_t sC,
+                    double *D, int64_t ldd, double alpha, double beta, int flags, int p0, int p1, int *path);
 
 /* ---- a4-a6: exact GP ------------------------------------------------------
  * MultiOutputExactGP.fit (exact_gp.py:476-499 -> ExactGP.fit :118-184) for
