@@ -167,6 +167,8 @@ _sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64,
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
 _sig("gpmpc_fleet_mc_detach", _c, _vp)
+_sig("gpmpc_nn_dist", _c, _vp, _dp, _c, _dp, _c, _c, _dp)
+_sig("gpmpc_select_diverse", _c, _vp, _dp, _c, _c, _dp, _c, ctypes.c_double, _c, _ip, _dp)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -206,7 +208,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_rollout6_records_dev", "gpmpc_comm_unique_id", "gpmpc_comm_init", "gpmpc_comm_destroy",
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
-            "gpmpc_fleet_query_launches", "gpmpc_gemm_diag"]
+            "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse"]
 
 
 class HIPError(RuntimeError):
@@ -708,6 +710,51 @@ def cov_propagate(ctx, A, q, S0=None, s0_diag=1e-6):
     _chk(_L.gpmpc_cov_propagate(ctx.h, B, N, nx, _d(A), _d(q), s0, float(s0_diag), _d(out)),
          "cov_propagate")
     return out
+
+
+# ---- novelty / diverse-subset selection (csrc/select.hip) ------------------------
+# the kernels' shape constants (csrc/select.hip; tests/test_select_host.py keeps them equal)
+NN_TILE = 128              # reference rows per LDS tile of gpmpc_nn_dist
+SELECT_ONE_THREADS = 512   # path 1's one workgroup
+SELECT_ONE_MAXN = 8192     # the most candidates path 1 takes
+SELECT_GRID_SLICE = 1024   # candidates per workgroup of path 2
+SELECT_CROSSOVER = 6144    # path 0: path 1 up to this n, path 2 above
+SELECT_MAXD = 32
+
+
+def _finite(a, what):
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{what} must be finite")
+
+
+def nn_dist(ctx, X, R):
+    """gpmpc_nn_dist: the distance of every row of X (n, d) to its nearest row of R (r, d),
+    bit-equal to ``np.min(np.linalg.norm(X[:, None] - R, axis=2), axis=1)``."""
+    X = f64(np.atleast_2d(X)); R = f64(np.atleast_2d(R))
+    n, d = X.shape
+    if R.shape[1] != d:
+        raise ValueError(f"nn_dist: X has {d} features, R {R.shape[1]}")
+    _finite(X, "nn_dist: X"); _finite(R, "nn_dist: R")
+    dist = np.empty(n)
+    _chk(_L.gpmpc_nn_dist(ctx.h, _d(X), n, _d(R), R.shape[0], d, _d(dist)), "nn_dist")
+    return dist
+
+
+def select_diverse(ctx, X, scores, n_select, diversity_weight=0.5, path=0):
+    """gpmpc_select_diverse: greedy farthest-point picking of n_select of the n rows of X
+    (n, d) by scores (n,) -> (indices (n_select,) in pick order, combined (n_select,) each
+    pick's winning value).  ``path``: 0 automatic, 1 / 2 force a kernel path."""
+    X = f64(np.atleast_2d(X)); n, d = X.shape
+    scores = f64(np.asarray(scores).reshape(-1))
+    if scores.size != n:
+        raise ValueError(f"select_diverse: {n} candidates, {scores.size} scores")
+    _finite(X, "select_diverse: X"); _finite(scores, "select_diverse: scores")
+    n_select = int(n_select)
+    m = max(n_select, 0)
+    idx = np.zeros(m, np.int32); comb = np.empty(m)
+    _chk(_L.gpmpc_select_diverse(ctx.h, _d(X), n, d, _d(scores), n_select, float(diversity_weight), int(path),
+                                 _i(idx), _d(comb)), "select_diverse")
+    return idx.astype(np.int64), comb
 
 
 # ---- diagnostic: the internal GEMM launchers (gpmpc_gemm_diag) -----------------

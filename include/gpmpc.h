@@ -585,6 +585,25 @@ int gpmpc_gather_prepare(gpmpc_ctx *ctx, gpmpc_comm *c, const double *d_records,
 int gpmpc_gather_collective(gpmpc_ctx *ctx, gpmpc_comm *c, const int *counts, int root, double *out);
 int gpmpc_fleet_destroy(gpmpc_fleet *f);
 
+/* ---- novelty / diverse-subset selection of GP training data ---------------
+ * Replaces the distance part of NoveltySelector._compute_distance_novelty
+ * (novelty_selector.py:154-170) and the greedy loop of NoveltySelector.select_diverse
+ * (:264-296).  Every squared distance is summed in numpy's order for
+ * np.linalg.norm(A - x, axis=1), so the results are numpy's bits.
+ *
+ * dist[i] = min_j |X[i] - R[j]|_2: X n x d, R r x d (host, row-major), dist n (host).
+ * 1 <= d <= 32, n >= 0, r >= 1. */
+int gpmpc_nn_dist(gpmpc_ctx *ctx, const double *X, int n, const double *R, int r, int d, double *dist);
+/* Greedy farthest-point picking: pick 0 = argmax(scores); pick t = argmax over the
+ * unselected i of scores[i] + diversity_weight * mind[i], mind[i] the distance of X[i] to
+ * the nearest pick so far (the reference's weight is 0.5); the lowest index wins equal
+ * values.  X n x d, scores n (host; finite); idx_out n_select picks in order,
+ * combined_out (n_select, may be NULL) each pick's winning value (pick 0: its score).
+ * 1 <= d <= 32, 1 <= n_select <= n.  path: 0 automatic, 1 one workgroup in one launch
+ * (n <= 8192, else -2), 2 a grid of workgroups with one launch per pick. */
+int gpmpc_select_diverse(gpmpc_ctx *ctx, const double *X, int n, int d, const double *scores, int n_select,
+                         double diversity_weight, int path, int *idx_out, double *combined_out);
+
 #ifdef __cplusplus
 }
 #endif
