@@ -164,6 +164,8 @@ _sig("gpmpc_fleet_destroy", _c, _vp)
 _i64 = ctypes.c_int64
 _sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64,
      ctypes.c_double, ctypes.c_double, _c, _c, _c, _ip)
+_sig("gpmpc_gemm_row_tiles", _c, _c, _c, _c, _ip)
+_sig("gpmpc_potrf_plan", _c, _c, _c, _ip, _ip, _ip, _c)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
 _sig("gpmpc_fleet_mc_detach", _c, _vp)
@@ -208,7 +210,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_rollout6_records_dev", "gpmpc_comm_unique_id", "gpmpc_comm_init", "gpmpc_comm_destroy",
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
-            "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse"]
+            "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
+            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan"]
 
 
 class HIPError(RuntimeError):
@@ -876,3 +879,37 @@ def gemm_diag(ctx, op, M, N, K, A=None, B=None, C=None, D=None, alpha=1.0, beta=
                             float(beta), int(flags), p0, p1, _i(path))
     _chk(rc, "gemm_diag")
     return GEMM_PATH[int(path[0])], int(path[1]), GEMM_GRID[int(path[2])]
+
+
+def gemm_row_tiles(M, N, K):
+    """(rows of the SUMSQ partial buffer its consumers sum, kind the launcher picks) for an
+    M x N x K product under this process's switches (gpmpc_gemm_row_tiles; no device)."""
+    kind = ctypes.c_int(-9)
+    return _L.gpmpc_gemm_row_tiles(int(M), int(N), int(K), ctypes.byref(kind)), kind.value
+
+
+# ---- diagnostic: the batched Cholesky's launch plan (gpmpc_potrf_plan; no device) ----
+# csrc/potrf_plan.h: PotrfPolicy's fields with their defaults ("auto" for the three-state ones)
+POTRF_POLICY = {"p128": 1, "persist": 0, "lat": -1, "sweep": 1, "trsm": -1, "pk": -1, "ob": 0, "ksplit": 0,
+                "fuse": 1, "la": 0, "syrk_diag": 1, "fuse_min": 0, "stamps": 0}
+POTRF_STEP = ["diag", "upd_syrk_diag", "upd_rowblock", "updsolve", "psolve_trsm", "psolve_lat", "psolve_rowblock",
+              "trail_lat", "trail_syrk"]
+POTRF_FORM = ["32", "persist", "128"]
+
+
+def potrf_plan(n, batch, **switches):
+    """The launches gpmpc_potrf_batched_dev makes for (n, batch): (form, steps), form a
+    POTRF_FORM name, each step (kind name, c, K0, four operands -- include/gpmpc.h).
+    Without keywords the plan follows this process's GPMPC_* switches; with any, it follows
+    the default policy with those fields of POTRF_POLICY replaced."""
+    unknown = set(switches) - set(POTRF_POLICY)
+    if unknown:
+        raise TypeError(f"potrf_plan: unknown switches {sorted(unknown)}")
+    pol = np.array(list(dict(POTRF_POLICY, **switches).values()), np.int32)
+    form = ctypes.c_int(-9)
+    cap = 4 * ((int(n) + 127) // 128) + 4   # at most an update, the factor, a solve and a trailing update per block
+    buf = np.zeros((cap, 7), np.int32)
+    cnt = _L.gpmpc_potrf_plan(int(n), int(batch), _i(pol) if switches else None, ctypes.byref(form), _i(buf), cap)
+    if cnt < 0 or cnt > cap:
+        _err(cnt, "potrf_plan")
+    return POTRF_FORM[form.value], [(POTRF_STEP[r[0]], *map(int, r[1:])) for r in buf[:cnt]]

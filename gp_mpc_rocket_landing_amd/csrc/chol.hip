@@ -18,6 +18,7 @@
 #include "mfma64.h"
 #include "gemm.h"
 #include "mma128.h"
+#include "potrf_plan.h"
 
 #define NB 32
 #define TP 34  // LDS pitch (doubles) for 32-wide tiles: conflict-free ds_read_b64
@@ -1272,232 +1273,99 @@ hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int6
 //   k_potrf_diag128            L_KK (global) and Linv = L_KK^-1 (scratch)
 //   A[t0:n, K0:t0] <- A[t0:n, K0:t0] Linv^T      (MFMA, K = 128, in place)
 //   A[t0:n, t0:n]  -= A[t0:n, K0:t0] A[t0:n, K0:t0]^T  (lower SYRK, K = 128)
+// in the right-looking form; which launches (n, batch) gets is potrf_plan's decision (potrf_plan.h)
+static_assert(POTRF_DB == DB, "potrf_plan.h plans in the driver's column blocks");
+static auto diag128_kernel(bool st, bool pk) {  // k_potrf_diag128<stamps, packed layout>
+  return pk ? (st ? k_potrf_diag128<true, true> : k_potrf_diag128<false, true>)
+            : (st ? k_potrf_diag128<true> : k_potrf_diag128<false>);
+}
+
+// diagnostic (GPMPC_DIAG128_STAMPS): accumulated phase cycles of workgroup 0 over all panels
+static void print_diag128_stamps(hipStream_t s) {
+  unsigned long long h[8];
+  (void)hipStreamSynchronize(s);
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_d128_stamps), sizeof(h));
+  fprintf(stderr, "diag128 cycles: load %llu diag %llu panel %llu trail0 %llu lout %llu inv %llu "
+                  "linvout %llu fac4 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+  const unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_d128_stamps), z, sizeof(h));
+  unsigned long long w[12];
+  (void)hipMemcpyFromSymbol(w, HIP_SYMBOL(g_sw_stamps), sizeof(w));
+  fprintf(stderr, "sweep (sum over panels) own start %llu %llu %llu %llu  own end %llu %llu %llu %llu  "
+                  "wave end %llu %llu %llu %llu\n", w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7],
+          w[8], w[9], w[10], w[11]);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sw_stamps), z, sizeof(z));
+  (void)hipMemcpyFromSymbol(w, HIP_SYMBOL(g_sw_step), 3 * sizeof(w[0]));
+  fprintf(stderr, "owner steps of block 0 (sum): pivots %llu stores %llu tiles %llu\n", w[0], w[1], w[2]);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sw_step), z, 3 * sizeof(z[0]));
+}
+
 static hipError_t launch_potrf_batched128(hipStream_t s, int n, int batch, double *A, int64_t lda,
-                                          int64_t stride, int *info, double *Linv) {
-  static const bool st = [] {
-    const char *e = getenv("GPMPC_DIAG128_STAMPS");
-    return e && atoi(e);
-  }();
+                                          int64_t stride, int *info, double *Linv, const PotrfPolicy &pol) {
   static bool attr = [] {
-    return hipFuncSetAttribute((const void *)k_potrf_diag128<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)DIAG128_LDS) == hipSuccess &&
-           hipFuncSetAttribute((const void *)k_potrf_diag128<true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)DIAG128_LDS) == hipSuccess &&
-           hipFuncSetAttribute((const void *)k_potrf_diag128<false, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)DIAG128_LDS_PK) == hipSuccess &&
-           hipFuncSetAttribute((const void *)k_potrf_diag128<true, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)DIAG128_LDS_PK) == hipSuccess;
+    bool ok = true;
+    for (int i = 0; i < 4; ++i)  // bit 0: stamps, bit 1: the packed layout
+      ok = ok && hipFuncSetAttribute((const void *)diag128_kernel(i & 1, i & 2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(i & 2 ? DIAG128_LDS_PK : DIAG128_LDS)) == hipSuccess;
+    return ok;
   }();
   if (!attr) return hipErrorInvalidConfiguration;
   hipError_t e = hipMemsetAsync(info, 0, sizeof(int) * batch, s);
   if (e != hipSuccess) return e;
   auto at = [&](int r, int c) { return A + (int64_t)r * lda + c; };
-  // few matrices: the panel solve and the trailing SYRK in the latency form
-  // (k_gemm_lat: one memory round trip per launch instead of K / 16);
-  // GPMPC_POTRF_LAT = 0 / 1 forces it off / on, default for batch <= lat_max
-  static const int lat_env = [] {
-    const char *v = getenv("GPMPC_POTRF_LAT");
-    return v ? atoi(v) : -1;
-  }();
-  const bool lat = lat_env >= 0 ? lat_env > 0 : batch <= 16;
-  // diagonal kernel: the column sweep (default) or the per-block inverse form
-  static const int sweep = [] {
-    const char *v = getenv("GPMPC_DIAG_SWEEP");
-    return v ? atoi(v) : 1;
-  }();
-  // panel solve in the TRSM form (k_potrf_psolve_lat) with the diagonal kernel's
-  // inverted 32 x 32 blocks, for the latency path (GPMPC_POTRF_TRSM=0: the full
-  // inverse and the latency GEMM)
-  static const int trsm_env = [] {
-    const char *v = getenv("GPMPC_POTRF_TRSM");
-    return v ? atoi(v) : -1;
-  }();
-  // (measured: batch 32 0.99 -> 0.86 ms, 64 1.35 -> 1.28 ms, 256 3.64 -> 3.75 ms)
-  const bool tblk = sweep && (trsm_env >= 0 ? trsm_env > 0 : batch <= 64);
-  // the diagonal kernel on the packed lower layout (74 KB of LDS: two workgroups per CU)
-  // where there are more matrices than CUs (GPMPC_DIAG_PK = 0 / 1: off / whenever the
-  // sweep runs)
-  static const int pk_env = [] {
-    const char *v = getenv("GPMPC_DIAG_PK");
-    return v ? atoi(v) : -1;
-  }();
-  const bool pk = sweep && (pk_env >= 0 ? pk_env > 0 : batch > 256);
-  // panel solve A[c+128:n, c:c+128] <- A[c+128:n, c:c+128] Linv^T (in place)
-  auto psolve = [&](int c) {
-    const int r = c + DB;
-    if (tblk) {
-      hipLaunchKernelGGL(k_potrf_psolve_lat, dim3((n - r + 15) / 16, 1, batch), dim3(256), 0, s,
-                         n - r, at(c, c), lda, Linv, at(r, c), stride, (int64_t)DB * DB, stride);
-      return hipGetLastError();
+  const int64_t sL = (int64_t)DB * DB;  // Linv: one 128 x 128 block per matrix
+  potrf_plan(n, batch, pol, [&](const PotrfStep &t) {
+    if (e != hipSuccess) return;  // an earlier launch failed: nothing more is launched
+    const int c = t.c, K0 = t.K0, r = c + DB, *a = t.a;
+    switch (t.kind) {
+      case POTRF_DIAG:
+        hipLaunchKernelGGL(diag128_kernel(pol.stamps, a[1]), dim3(batch), dim3(256), a[1] ? DIAG128_LDS_PK : DIAG128_LDS,
+                           s, n, c, A, lda, stride, info, a[3] ? Linv : nullptr, a[2]);
+        break;
+      case POTRF_UPD_SYRK_DIAG:
+        e = launch_syrk128_diag(s, a[0], a[1], at(c, K0), lda, at(c, c), batch, stride, a[2]);
+        break;
+      case POTRF_UPD_ROWBLOCK:
+        e = launch_gemm_nt_rowblock(s, a[0], a[1], a[2], at(c, K0), lda, at(c, K0), lda, at(c, c), lda, -1.0, 1.0,
+                                    batch, stride, stride, stride, 1, a[3]);
+        break;
+      case POTRF_UPDSOLVE:
+        e = launch_gemm_updsolve(s, a[0], a[1], at(r, K0), lda, at(c, K0), at(r, c), Linv, batch, stride, stride, sL,
+                                 a[2]);
+        break;
+      case POTRF_PSOLVE_TRSM:
+        hipLaunchKernelGGL(k_potrf_psolve_lat, dim3((a[0] + 15) / 16, 1, batch), dim3(256), 0, s, a[0], at(c, c), lda,
+                           Linv, at(r, c), stride, sL, stride);
+        e = hipGetLastError();
+        break;
+      case POTRF_PSOLVE_LAT:
+        e = launch_gemm_lat(s, 0, a[0], DB, DB, at(r, c), lda, Linv, DB, at(r, c), lda, 1.0, 0.0, 1, batch, stride, sL,
+                            stride);
+        break;
+      case POTRF_PSOLVE_ROWBLOCK:
+        e = launch_gemm_nt_rowblock(s, a[0], DB, DB, at(r, c), lda, Linv, DB, at(r, c), lda, 1.0, 0.0, batch, stride,
+                                    sL, stride);
+        break;
+      case POTRF_TRAIL_LAT:
+        e = launch_gemm_lat(s, 1, a[0], a[0], a[1], at(c, K0), lda, nullptr, lda, at(c, c), lda, -1.0, 1.0, 0, batch,
+                            stride, stride, stride);
+        break;
+      case POTRF_TRAIL_SYRK:
+        e = launch_gemm_nt(s, EPI_STORE, a[0], a[0], a[1], at(c, K0), lda, at(c, K0), lda, at(c, c), lda, -1.0, 1.0, 0,
+                           1, batch, stride, stride, stride);
+        break;
     }
-    if (lat)
-      return launch_gemm_lat(s, 0, n - r, DB, DB, at(r, c), lda, Linv, DB, at(r, c), lda, 1.0, 0.0,
-                             1, batch, stride, (int64_t)DB * DB, stride);
-    return launch_gemm_nt_rowblock(s, n - r, DB, DB, at(r, c), lda, Linv, DB, at(r, c), lda, 1.0,
-                                   0.0, batch, stride, (int64_t)DB * DB, stride);
-  };
-  // Outer panels of OB = 128 m columns.  Inside a panel, 128-column steps are
-  // left-looking (a step's columns take the update of the panel's earlier
-  // steps, K = c - K0); across panels, one lower SYRK with K = OB, so the
-  // O(n^3) work runs as K = OB products (fewer C read-modify-writes, longer K).
-  // Default: 128 (right-looking, K = 128 SYRKs) below batch 128, 1024 (left-looking:
-  // each 128-column block takes the update of all earlier columns, K = c, with no
-  // trailing SYRK) from 256 on and from 128 for multiples of 8 (the fused steps) --
-  // measured at n = 1000 (round 3, unfused): 64: 1.34 vs 1.60 ms, 256: 3.62 vs 3.58 ms,
-  // 1024: 13.6 vs 13.2 ms.  256-512: no better than either.
-  static const int ob_env = [] {
-    const char *v = getenv("GPMPC_POTRF_OB");
-    if (!v) return 0;
-    const int m = atoi(v) / DB;
-    return DB * (m < 1 ? 1 : m > 8 ? 8 : m);
-  }();
-  // left-looking from batch 128 when the fused steps apply (a multiple of 8): measured at
-  // n = 1000, 128: 2.13 -> 1.95 ms, 192: 2.89 -> 2.54 ms; 64 stays right-looking (1.25 vs 1.36)
-  const int OBk = ob_env ? ob_env : ((batch >= 256 || (batch >= 128 && batch % 8 == 0)) ? 8 * DB : DB);
-  static const int ksplit_env = [] {
-    const char *v = getenv("GPMPC_POTRF_KSPLIT");
-    return v ? atoi(v) : 0;
-  }();
-  // Left-looking block columns, fused: the diagonal block's update alone, the diagonal
-  // kernel, then ONE pass over the rows below (update + panel solve, k_gemm128_updsolve)
-  // instead of an update launch over all rows and a panel-solve launch; for batches that
-  // are a multiple of 8 whose rows below fill >= 512 workgroups (GPMPC_POTRF_FUSE=0: off)
-  static const int fuse_env = [] {
-    const char *v = getenv("GPMPC_POTRF_FUSE");
-    return v ? atoi(v) : 1;
-  }();
-  const bool fuse_ok = fuse_env && OBk > DB && !tblk && !lat && batch % 8 == 0;
-  // look-ahead (GPMPC_POTRF_LA=1): a fused step's first row tile also applies the next
-  // fused step's diagonal-block update (k_gemm128_updsolve<true>), so that launch goes.
-  // Off: the first row tiles become the launch's stragglers (batch 1024: 11.6 -> 15.0 ms)
-  static const int la_env = [] {
-    const char *v = getenv("GPMPC_POTRF_LA");
-    return v ? atoi(v) : 0;
-  }();
-  // the diagonal block's update by the balanced lower-triangle kernel (k_syrk128_diag,
-  // 9 MFMA blocks per wave) instead of the 128-tile kernel's quadrants (GPMPC_SYRK_DIAG=0)
-  static const int syrk_diag_env = [] {
-    const char *v = getenv("GPMPC_SYRK_DIAG");
-    return v ? atoi(v) : 1;
-  }();
-  // a block column fuses when its rows below fill >= GPMPC_POTRF_FUSE_MIN workgroups (512)
-  static const int fuse_min_env = [] {
-    const char *v = getenv("GPMPC_POTRF_FUSE_MIN");
-    return v ? atoi(v) : 0;
-  }();
-  // (batch 128: 512 -> 1.88 ms, 1 -> 1.95 ms; 256-1024: no difference)
-  const int fuse_min = fuse_min_env ? fuse_min_env : 512;
-  auto fuses = [&](int c) {
-    const int below = n - c - min(DB, n - c);
-    return fuse_ok && below > 0 && (below + DB - 1) / DB * batch >= fuse_min;
-  };
-  for (int K0 = 0; K0 < n; K0 += OBk) {
-    const int pw = min(OBk, n - K0);
-    bool la_prev = false;  // this step's diagonal update was applied by the previous step
-    for (int c = K0; c < K0 + pw; c += DB) {
-      const int w = min(DB, n - c);
-      const int below = n - c - w;
-      const bool fuse = fuses(c);
-      const bool la = la_env && fuse && w == DB && c + DB < K0 + pw && fuses(c + DB);
-      if (c > K0 && fuse && la_prev) {
-        // the diagonal block's update came with the previous step's first row tile
-      } else if (c > K0 && fuse) {
-        // the diagonal block's rows only (one tile per matrix), K split to fill the device
-        const int K = c - K0;
-        int ks = 1;
-        if (ksplit_env != 1)
-          while (ks < K / DB && batch * ks < 512) ++ks;
-        e = syrk_diag_env ? launch_syrk128_diag(s, w, K, at(c, K0), lda, at(c, c), batch, stride, ks)
-                          : launch_gemm_nt_rowblock(s, w, w, K, at(c, K0), lda, at(c, K0), lda, at(c, c), lda, -1.0,
-                                                    1.0, batch, stride, stride, stride, 1, ks);
-        if (e != hipSuccess) return e;
-      } else if (c > K0) {
-        // the block column's update by all earlier columns of the outer panel; K split
-        // (atomic partial sums) when its row tiles give fewer than ~2 workgroups per CU,
-        // >= 128 of K per split (GPMPC_POTRF_KSPLIT=1: never)
-        const int K = c - K0, tiles = (n - c + DB - 1) / DB * batch;
-        int ks = 1;
-        if (ksplit_env != 1)
-          while (ks < K / DB && tiles * ks < 512) ++ks;
-        // the last block column of a left-looking panel has no rows below: its diagonal block alone
-        e = (syrk_diag_env && OBk > DB && n - c == w)
-                ? launch_syrk128_diag(s, w, K, at(c, K0), lda, at(c, c), batch, stride, ks)
-                : launch_gemm_nt_rowblock(s, n - c, w, K, at(c, K0), lda, at(c, K0), lda, at(c, c), lda,
-                                          -1.0, 1.0, batch, stride, stride, stride, 1, ks);
-        if (e != hipSuccess) return e;
-      }
-      if (pk && st)
-        hipLaunchKernelGGL((k_potrf_diag128<true, true>), dim3(batch), dim3(256), DIAG128_LDS_PK, s, n, c, A,
-                           lda, stride, info, c + DB < n ? Linv : nullptr, sweep | (tblk ? 2 : 0));
-      else if (pk)
-        hipLaunchKernelGGL((k_potrf_diag128<false, true>), dim3(batch), dim3(256), DIAG128_LDS_PK, s, n, c, A,
-                           lda, stride, info, c + DB < n ? Linv : nullptr, sweep | (tblk ? 2 : 0));
-      else if (st)
-        hipLaunchKernelGGL(k_potrf_diag128<true>, dim3(batch), dim3(256), DIAG128_LDS, s, n, c, A,
-                           lda, stride, info, c + DB < n ? Linv : nullptr, sweep | (tblk ? 2 : 0));
-      else
-        hipLaunchKernelGGL(k_potrf_diag128<false>, dim3(batch), dim3(256), DIAG128_LDS, s, n, c,
-                           A, lda, stride, info, c + DB < n ? Linv : nullptr, sweep | (tblk ? 2 : 0));
-      if (fuse) {
-        e = launch_gemm_updsolve(s, below, c - K0, at(c + w, K0), lda, at(c, K0), at(c + w, c), Linv, batch,
-                                 stride, stride, (int64_t)DB * DB, la ? min(DB, below) : 0);
-        if (e != hipSuccess) return e;
-      } else if (c + DB < n && (e = psolve(c)) != hipSuccess) {
-        return e;
-      }
-      la_prev = la;
-    }
-    const int t0 = K0 + pw;
-    if (t0 < n) {
-      if (lat && pw <= DB)
-        e = launch_gemm_lat(s, 1, n - t0, n - t0, pw, at(t0, K0), lda, nullptr, lda, at(t0, t0),
-                            lda, -1.0, 1.0, 0, batch, stride, stride, stride);
-      else
-        e = launch_gemm_nt(s, EPI_STORE, n - t0, n - t0, pw, at(t0, K0), lda, at(t0, K0), lda,
-                           at(t0, t0), lda, -1.0, 1.0, 0, 1, batch, stride, stride, stride);
-      if (e != hipSuccess) return e;
-    }
-  }
-  if (st) {  // diagnostic: accumulated phase cycles of workgroup 0 over all panels
-    unsigned long long h[8];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_d128_stamps), sizeof(h));
-    fprintf(stderr, "diag128 cycles: load %llu diag %llu panel %llu trail0 %llu lout %llu inv %llu "
-                    "linvout %llu fac4 %llu\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-    const unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_d128_stamps), z, sizeof(h));
-    unsigned long long w[12];
-    (void)hipMemcpyFromSymbol(w, HIP_SYMBOL(g_sw_stamps), sizeof(w));
-    fprintf(stderr, "sweep (sum over panels) own start %llu %llu %llu %llu  own end %llu %llu %llu %llu  "
-                    "wave end %llu %llu %llu %llu\n", w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7],
-            w[8], w[9], w[10], w[11]);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sw_stamps), z, sizeof(z));
-    (void)hipMemcpyFromSymbol(w, HIP_SYMBOL(g_sw_step), 3 * sizeof(w[0]));
-    fprintf(stderr, "owner steps of block 0 (sum): pivots %llu stores %llu tiles %llu\n", w[0], w[1], w[2]);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sw_step), z, 3 * sizeof(z[0]));
-  }
+  });
+  if (e != hipSuccess) return e;
+  if (pol.stamps) print_diag128_stamps(s);
   return hipGetLastError();
 }
 
 hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int64_t lda,
                                 int64_t stride, int *info) {
-  static const int p128 = [] {
-    const char *e = getenv("GPMPC_POTRF128");
-    return e ? atoi(e) : 1;
-  }();
-  // one workgroup per matrix (GPMPC_POTRF_PERSIST=1; read per call, tests switch
-  // it).  Off by default: measured 3.67 ms per round of <= 256 matrices of
-  // n = 1000 (20.8% of FP64 peak at batch 256) against 3.9 ms (28%) for the
-  // launch-per-panel path -- one wave per SIMD (130 KB of LDS per workgroup)
-  // leaves the MFMA tile loop's LDS and barrier latency exposed, and the
-  // diagonal chain idles the CU.
-  const char *pe = getenv("GPMPC_POTRF_PERSIST");
-  const bool persist = pe && atoi(pe) > 0;
-  if (p128 && persist) {
+  const PotrfPolicy pol = potrf_policy_env();
+  const int form = potrf_form(pol);
+  if (form == POTRF_FORM_PERSIST) {
     static bool attr = hipFuncSetAttribute((const void *)k_potrf_persist,
                                            hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)DIAG128_LDS) == hipSuccess;
@@ -1510,10 +1378,10 @@ hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int6
                        info, Lws);
     return hipGetLastError();
   }
-  if (p128) {
+  if (form == POTRF_FORM_128) {
     double *Linv = (double *)gpmpc_scratch(s, 2, sizeof(double) * DB * DB * (size_t)batch);
     if (!Linv) return hipErrorOutOfMemory;
-    return launch_potrf_batched128(s, n, batch, A, lda, stride, info, Linv);
+    return launch_potrf_batched128(s, n, batch, A, lda, stride, info, Linv, pol);
   }
   double *Linv = (double *)gpmpc_scratch(s, 1, sizeof(double) * NB * NB * (size_t)batch);
   if (!Linv) return hipErrorOutOfMemory;
@@ -1796,6 +1664,24 @@ extern "C" int gpmpc_potrf_batched_dev(gpmpc_ctx *ctx, int n, int batch, double 
   GPMPC_HIP(hipSetDevice(ctx->device));
   GPMPC_HIP(launch_potrf_batched(ctx->stream, n, batch, dA, lda, stride, dinfo));
   return 0;
+}
+
+// diagnostic: the plan launch_potrf_batched would execute, no device touched
+static_assert(sizeof(PotrfPolicy) == GPMPC_POTRF_POLICY_N * sizeof(int) &&
+              sizeof(PotrfStep) == GPMPC_POTRF_STEP_INTS * sizeof(int), "gpmpc_potrf_plan's layouts");
+extern "C" int gpmpc_potrf_plan(int n, int batch, const int *policy, int *form, int *steps, int cap) {
+  GPMPC_CHECK_ARG(n >= 0 && batch >= 0 && form && cap >= 0 && (steps || cap == 0));
+  PotrfPolicy pol = potrf_policy_env();
+  if (policy) memcpy(&pol, policy, sizeof(pol));
+  GPMPC_CHECK_ARG(pol.ob >= 0 && pol.ob <= 8 * DB && pol.ob % DB == 0);
+  *form = potrf_form(pol);
+  int count = 0;
+  if (*form == POTRF_FORM_128 && batch > 0)
+    potrf_plan(n, batch, pol, [&](const PotrfStep &t) {
+      if (count < cap) memcpy(steps + GPMPC_POTRF_STEP_INTS * count, &t, sizeof(t));
+      ++count;
+    });
+  return count;
 }
 
 static int trsm_host(gpmpc_ctx *ctx, int n, int nrhs, const double *L, int ldl, double *B, int ldb,

@@ -13,6 +13,11 @@ void gpmpc_set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
+int gpmpc_env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // Persistent device scratch per (stream, slot), grown with hipMalloc after the
 // stream has drained.  Every context owns one stream, so two contexts (e.g. on
 // two threads) never share a buffer; gpmpc_ctx_destroy releases its stream's

@@ -25,6 +25,7 @@
 #include "gemm.h"
 #include "qp.h"
 #include "fleet_qp.h"
+#include <climits>
 #include <mutex>
 #include <vector>
 #include <algorithm>
@@ -1353,17 +1354,13 @@ static int fleet_create(gpmpc_ctx *ctx, gpmpc_gp *gp, gpmpc_fitc *fitc, const gp
     hipMemcpyAsync(f->order.p, id.data(), sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream);
     GPMPC_HIP(hipStreamSynchronize(ctx->stream));
   }
-  const char *oe = getenv("GPMPC_FLEET_ORDER");
-  f->use_order = !oe || atoi(oe) != 0;
-  const char *aw = getenv("GPMPC_FLEET_ALTWAVE");
-  f->alt_wave = aw ? atoi(aw) != 0 : 0;
-  const char *sp = getenv("GPMPC_FLEET_SIMD");
-  f->simd_pick = !sp || atoi(sp) != 0;
-  const char *fp = getenv("GPMPC_FLEET_FUSE_POST");
-  f->fuse_post = !fp || atoi(fp) != 0;
-  const char *se = getenv("GPMPC_FLEET_SOLVER");
+  // the fleet's switches, read at creation
+  f->use_order = gpmpc_env_int("GPMPC_FLEET_ORDER", 1) != 0;
+  f->alt_wave = gpmpc_env_int("GPMPC_FLEET_ALTWAVE", 0) != 0;
+  f->simd_pick = gpmpc_env_int("GPMPC_FLEET_SIMD", 1) != 0;
+  f->fuse_post = gpmpc_env_int("GPMPC_FLEET_FUSE_POST", 1) != 0;
   // the specialised solver assumes the N = 20 stage layout of its LDS caps
-  f->use_fq = (!se || atoi(se) != 0) && N == 20 && f->pat.mode == 1 && f->pat.nblk == FQ_NBLK &&
+  f->use_fq = gpmpc_env_int("GPMPC_FLEET_SOLVER", 1) != 0 && N == 20 && f->pat.mode == 1 && f->pat.nblk == FQ_NBLK &&
               m - n == FQ_MD && f->pat.nnz - n == FQ_NNZD;
   // small fleets (at most one landing per CU) take the 256-thread, one-wave-per-SIMD build of
   // the control kernel: twice the threads for the parallel ADMM phases and no register
@@ -1372,8 +1369,8 @@ static int fleet_create(gpmpc_ctx *ctx, gpmpc_gp *gp, gpmpc_fitc *fitc, const gp
   // = 0 / 1 forces it)
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  const char *we = getenv("GPMPC_FLEET_WIDE");
-  f->wide = f->use_fq && (we ? atoi(we) != 0 : fleet_batch <= cus);
+  const int we = gpmpc_env_int("GPMPC_FLEET_WIDE", INT_MIN);  // (unset: by the fleet size)
+  f->wide = f->use_fq && (we != INT_MIN ? we != 0 : fleet_batch <= cus);
   GPMPC_HIP(hipStreamSynchronize(ctx->stream));
   *out = f;
   return 0;
@@ -1432,10 +1429,7 @@ static hipError_t fleet_gp_posterior(gpmpc_fleet *f, int mask) {
   // each of the 8 row tiles regenerates its K* columns (4.6x the exps of the
   // gram kernel) and the exp/scalar-load stream does not hide under the FP64
   // MFMAs at 2 waves per SIMD.  Off by default.
-  static const int fused_env = [] {
-    const char *v = getenv("GPMPC_POST_FUSED");
-    return v ? atoi(v) : 0;
-  }();
+  static const int fused_env = gpmpc_env_int("GPMPC_POST_FUSED", 0);
   // GPMPC_POST_CS=1: the column-stationary posterior (post.hip), K* formed once per
   // workgroup inside the MFMA pass, never in HBM; two partial rows
   const bool cs = !f->fitc && g.Wf && post_cs_env();
@@ -1451,10 +1445,7 @@ static hipError_t fleet_gp_posterior(gpmpc_fleet *f, int mask) {
     // GPMPC_GRAM_FEAT=0: the query rows from a launch of their own (k_fleet_queries -> Q).
     // Default: the row-tiled Gram kernel forms its 128 rows itself (same function, same
     // bits), one launch and the Q round trip less; Q is then not written.
-    static const bool feat_env = [] {
-      const char *v = getenv("GPMPC_GRAM_FEAT");
-      return !v || atoi(v) != 0;
-    }();
+    static const int feat_env = gpmpc_env_int("GPMPC_GRAM_FEAT", 1);
     const FleetPlans pl{f->Xw.as<double>(), f->Uw.as<double>(), g.ls, f->use_order ? f->order.as<int>() : nullptr,
                         f->N, g.kind == GPMPC_SE_ISO};
     const bool in_gram = feat_env && !fused && !cs && g.d == NFEAT && gram_rows_tiled(P, g.d);

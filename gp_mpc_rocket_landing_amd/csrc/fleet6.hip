@@ -259,8 +259,7 @@ extern "C" int gpmpc_rollout6_create_exact(gpmpc_ctx *ctx, gpmpc_gp *gp_v, gpmpc
 // of a point are split by whole waves, so every split gives the same bits.
 // GPMPC_R6_SPLIT=0 keeps one workgroup per rollout (read at every step).
 static int r6_predict_parts(int B, int cus) {
-  const char *e = getenv("GPMPC_R6_SPLIT");
-  if (e && atoi(e) == 0) return 1;
+  if (gpmpc_env_int("GPMPC_R6_SPLIT", 1) == 0) return 1;
   return (cus > 0 && 4 * ((B + 7) / 8) * 8 <= cus) ? 4 : 1;
 }
 
@@ -312,13 +311,7 @@ extern "C" int gpmpc_rollout6_reset(gpmpc_rollout6 *r, int first, int count, con
   return 0;
 }
 
-static bool r6_stamps_on() {
-  static const bool on = [] {
-    const char *e = getenv("GPMPC_R6_STAMPS");
-    return e && atoi(e) > 0;
-  }();
-  return on;
-}
+static bool r6_stamps_on() { static const int on = gpmpc_env_int("GPMPC_R6_STAMPS", 0); return on > 0; }
 
 extern "C" int gpmpc_rollout6_step_phases(gpmpc_rollout6 *r, int mask) {
   GPMPC_CHECK_ARG(r);

@@ -1473,10 +1473,7 @@ static hipError_t r6_init() {
   return e;
 }
 static void r6_launch_predict(hipStream_t s, int B, const R6Args &a0, bool st) {
-  static const int cap = [] {
-    const char *v = getenv("GPMPC_R6_PCACHE");
-    return v ? atoi(v) : R6_PCACHE_ROWS;
-  }();
+  static const int cap = gpmpc_env_int("GPMPC_R6_PCACHE", R6_PCACHE_ROWS);
   static const bool attr = [] {
     const int mx = (int)(sizeof(double) * (13 + 12) * R6_PCACHE_ROWS);  // the largest dynamic size used
     return hipFuncSetAttribute((const void *)k_r6_predict<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) ==

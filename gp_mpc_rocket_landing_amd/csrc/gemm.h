@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstdlib>
 
 enum { EPI_STORE = 0, EPI_SUMSQ = 1 };
 
@@ -104,10 +103,6 @@ hipError_t launch_post_cs(hipStream_t s, int n, int n_out, int P, const double *
 #define POST_CS_PARTS 2
 bool post_cs_env();  // GPMPC_POST_CS (default 0)
 
-// rows of the SUMSQ partial buffer for an M x N x K product (tile height of
-// the kernel launch_gemm_* picks: 128 when M, N and K >= 256, else 64)
-inline int gemm_row_tiles(int M, int N = 0, int K = 0) {
-  const char *e = getenv("GPMPC_GEMM128");
-  const bool big = (!e || atoi(e)) && M >= 256 && N >= 256 && K >= 256;
-  return big ? (M + 127) / 128 : (M + 63) / 64;
-}
+// rows of the SUMSQ partial buffer for an M x N x K product: the tile height of the
+// kernel launch_gemm_* picks, by the launcher's own rule (gemm_sumsq_kind)
+inline int gemm_row_tiles(int M, int N = 0, int K = 0) { return gemm_sumsq_rows(gemm_sumsq_kind(M, N, K), M); }

@@ -260,13 +260,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt(int M, int N, int K, const doub
 }
 
 // GPMPC_POST_XCD=1: the posterior GEMM's column-grouped XCD mapping (k_gemm128, tri_grid 2)
-static int post_xcd() {
-  static const int v = [] {
-    const char *e = getenv("GPMPC_POST_XCD");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int post_xcd() { static const int v = gpmpc_env_int("GPMPC_POST_XCD", 0); return v; }
 
 // ---------------------------------------------------------------------------
 // Large-tile variant: 128 x 128 per workgroup, each wave a 64 x 64 quadrant
@@ -950,13 +944,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(int M, int N, int S, cons
   }
 }
 
-static bool splitk_env() {
-  static const int v = [] {
-    const char *e = getenv("GPMPC_SPLITK");
-    return e ? atoi(e) : 1;
-  }();
-  return v != 0;
-}
+static bool splitk_env() { static const int v = gpmpc_env_int("GPMPC_SPLITK", 1); return v != 0; }
 
 // form: 0 NT (A M x K, B N x K), 1 NN (B K x N), 2 TN (A K x M, B K x N).  Returns false
 // (nothing launched) when the product is not skinny enough or scratch is unavailable.
@@ -1048,21 +1036,9 @@ static bool launch_splitk_sumsq(hipStream_t s, int M, int N, int K, const double
   return true;
 }
 
-static int gemm_big_env() {
-  static const int v = [] {
-    const char *e = getenv("GPMPC_GEMM128");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+static int gemm_big_env() { static const int v = gpmpc_env_int("GPMPC_GEMM128", 1); return v; }
 
-static int gemm_kmin_env() {
-  static const int v = [] {
-    const char *e = getenv("GPMPC_GEMM128_KMIN");
-    return e ? atoi(e) : 2 * BT;
-  }();
-  return v;
-}
+static int gemm_kmin_env() { static const int v = gpmpc_env_int("GPMPC_GEMM128_KMIN", 2 * BT); return v; }
 
 // The kernel launch_gemm_sumsq_mean picks for an (M x K) [W; alpha^T] against N query
 // rows (batch 1, triangular A): the rules of launch_gemm_impl below.  A caller whose column
@@ -1090,15 +1066,9 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
   // quantise badly (1.1-1.25 rounds: 21-36% vs 44-50% for 64-tiles).  FITC
   // 2000 x 4000: 128-tiles + split-K 56% vs 39%
   const int t128 = ((M + BT - 1) / BT) * ((M + BT - 1) / BT + 1) / 2 * batch;
-  static const int syrk128_env = [] {
-    const char *e = getenv("GPMPC_SYRK128");
-    return e ? atoi(e) : -1;
-  }();
+  static const int syrk128_env = gpmpc_env_int("GPMPC_SYRK128", -1);
   const bool tri_ok = !tg || (syrk128_env >= 0 ? syrk128_env != 0 : t128 >= 1024 || K >= 1024);
-  static const int sk_env = [] {
-    const char *e = getenv("GPMPC_STREAMK");
-    return e ? atoi(e) : -1;
-  }();
+  static const int sk_env = gpmpc_env_int("GPMPC_STREAMK", -1);
   // stream-K for long accumulations into C on big tiles: measured 2000^2 x 4000
   // 60% (split-K 55%), 4000^2 x 4000 72%, 16 x 1000^2 x 1000 56% (64-tiles 52%);
   // smaller or shorter products (n ~ 500, K <= 256) keep the tiled kernels
@@ -1133,10 +1103,7 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
         if (c < best * 0.98) best = c, ksplit = ks;
       }
     }
-    static const int ks_env = [] {
-      const char *e = getenv("GPMPC_KSPLIT");
-      return e ? atoi(e) : 0;
-    }();
+    static const int ks_env = gpmpc_env_int("GPMPC_KSPLIT", 0);
     if (ks_env > 0 && epi == EPI_STORE && beta == 1.0) ksplit = ks_env;
     // lower-triangular square products launch only their lower tiles, in a
     // 1-D order that interleaves them over the 8 XCDs (a 2-D grid whose
@@ -1158,20 +1125,15 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
     if (launch_splitk(s, 0, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
   }
   if (epi == EPI_SUMSQ && batch == 1 &&
-      (kind >= 0 ? kind == GEMM_SUMSQ_SPLITK : gemm_row_tiles(M, N, K) == (M + GT - 1) / GT)) {
+      (kind >= 0 ? kind == GEMM_SUMSQ_SPLITK : gemm_sumsq_kind(M, N, K) != GEMM_SUMSQ_128)) {
     hipError_t e = hipSuccess;  // (a triangular A's zero chunks are multiplied: the split is latency work)
     if (launch_splitk_sumsq(s, M, N, K, A, lda, B, ldb, C, ldc, msum, Cm, ldm, e)) return e;
   }
   const int tx = (N + GT - 1) / GT, ty = (M + GT - 1) / GT;
-  static const int remap_env = [] {
-    const char *e = getenv("GPMPC_GEMM_REMAP");
-    return e ? atoi(e) : 0;  // measured slower for the posterior GEMM (W blocks thrash)
-  }();
+  // (off: measured slower for the posterior GEMM, W blocks thrash)
+  static const int remap_env = gpmpc_env_int("GPMPC_GEMM_REMAP", 0);
   const bool remap = remap_env && batch == 1 && ty > 1 && tx % 8 == 0;
-  static const int xb_env = [] {
-    const char *e = getenv("GPMPC_XCD_BATCH");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xb_env = gpmpc_env_int("GPMPC_XCD_BATCH", 1);
   const int T = ty * (ty + 1) / 2;
   const int xb = (tg && xb_env && batch >= 8) ? batch : 0;
   dim3 g = xb ? dim3(T * ((batch + 7) / 8) * 8, 1, 1)
@@ -1242,10 +1204,7 @@ hipError_t launch_gemm_nt_rowblock(hipStream_t s, int M, int N, int K, const dou
   if (ksplit < 1 || beta != 1.0) ksplit = 1;
   dim3 g(1, (M + BT - 1) / BT, batch * ksplit);
   // a batch of >= 8 matrices (a multiple of 8): each matrix's row tiles on one XCD
-  static const int xb_env = [] {
-    const char *e = getenv("GPMPC_ROWBLOCK_XCD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xb_env = gpmpc_env_int("GPMPC_ROWBLOCK_XCD", 1);
   const int tg = (xb_env && batch >= 8 && batch % 8 == 0) ? 3 : 0;
   gemm_path(ksplit > 1 ? PATH_128_KSPLIT : PATH_128, ksplit, tg ? GRID_ROWBLOCK_XCD : GRID_2D);
   hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
@@ -1272,6 +1231,13 @@ hipError_t launch_gemm_sumsq_mean(hipStream_t s, int n, int n_out, int P, const 
                                   int64_t ldm, int kind) {
   return launch_gemm_impl(s, EPI_SUMSQ, n + n_out, P, n, Wext, n, Ks, n, part, ldp, 1.0, 0.0, 1, 0,
                           1, 0, 0, 0, n, meanT, ldm, kind);
+}
+
+// diagnostic, no device: what the SUMSQ consumers size their partial buffer by, and the
+// kernel the launcher would pick for the same product under this process's switches
+extern "C" int gpmpc_gemm_row_tiles(int M, int N, int K, int *kind) {
+  if (kind) *kind = gemm_sumsq_kind(M, N, K);
+  return gemm_row_tiles(M, N, K);
 }
 
 // ---------------------------------------------------------------------------

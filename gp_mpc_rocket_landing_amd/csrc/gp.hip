@@ -270,10 +270,7 @@ static hipError_t core_gram(hipStream_t s, const GpCore &g, const double *A, con
 // GPMPC_POST_CS=1: the column-stationary posterior (post.hip) instead of K* in HBM (gram +
 // 128-tile SUMSQ GEMM).  Off by default: measured slower at the bench workload (DESIGN.md
 // section 3).  Read at every fit and predict, so a process can switch it between handles.
-bool post_cs_env() {
-  const char *e = getenv("GPMPC_POST_CS");
-  return e && atoi(e) != 0;
-}
+bool post_cs_env() { return gpmpc_env_int("GPMPC_POST_CS", 0) != 0; }
 
 // Wf / Xp for the column-stationary posterior (post.hip) from the current [W; alpha^T],
 // Xs, Xn; released when the GP is outside the kernel's range
@@ -516,10 +513,7 @@ static hipError_t cho_solve_inv(hipStream_t s, int n, int nc, const double *L, c
 }
 
 static bool potrs_cols_ok(int n) {
-  static const int env = [] {
-    const char *e = getenv("GPMPC_POTRS_COLS");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = gpmpc_env_int("GPMPC_POTRS_COLS", 1);
   static const bool attr = hipFuncSetAttribute((const void *)k_potrs_cols,
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)(sizeof(double) * POTRS_COLS_MAXN)) == hipSuccess;
@@ -596,10 +590,7 @@ static int exact_fit(gpmpc_ctx *ctx, int kind, const double *X, int n, int d, co
   // W = L^-1 (identity right-hand side, lower-triangular result): the doubling inverse,
   // or the blocked TRSM (GPMPC_TRI_INV=0, n <= 128)
   hipLaunchKernelGGL(k_eye, dim3((n + 255) / 256, n), dim3(256), 0, s, n, g.W.as<double>());
-  static const int tri_inv_env = [] {
-    const char *e = getenv("GPMPC_TRI_INV");
-    return e ? atoi(e) : 1;
-  }();
+  static const int tri_inv_env = gpmpc_env_int("GPMPC_TRI_INV", 1);
   const bool inv = tri_inv_env && n > 128;
   {
     DevBuf tinv;
@@ -614,10 +605,7 @@ static int exact_fit(gpmpc_ctx *ctx, int kind, const double *X, int n, int d, co
   }
   // alpha = L^-T L^-1 y for all outputs: through W with one refinement step
   // (GPMPC_ALPHA_INV=0: the per-column substitution kernel, or the blocked TRSMs)
-  static const int alpha_inv_env = [] {
-    const char *e = getenv("GPMPC_ALPHA_INV");
-    return e ? atoi(e) : 1;
-  }();
+  static const int alpha_inv_env = gpmpc_env_int("GPMPC_ALPHA_INV", 1);
   hipError_t ea = hipSuccess;
   if (alpha_inv_env) {
     ea = cho_solve_inv(s, n, n_out, gp->L.as<double>(), g.W.as<double>(), dY.as<double>());
@@ -1212,8 +1200,7 @@ int fitc_posterior_dev(gpmpc_ctx *ctx, gpmpc_fitc *gp, const double *dq, int p, 
   const GpCore &g = gp->core;
   const int m = gp->m;
   // small inducing sets: one launch (GPMPC_FITC_SMALL=0: the GEMM form at every size)
-  const char *fs = getenv("GPMPC_FITC_SMALL");
-  if ((!fs || atoi(fs)) && m <= FITC_SMALL_M && g.d <= FITC_SMALL_D && g.n_out <= FITC_SMALL_NO &&
+  if (gpmpc_env_int("GPMPC_FITC_SMALL", 1) && m <= FITC_SMALL_M && g.d <= FITC_SMALL_D && g.n_out <= FITC_SMALL_NO &&
       g.kind != GPMPC_KPROG) {
     hipLaunchKernelGGL(k_fitc_post_small, dim3(p), dim3(256), 0, s, fitc_view(gp), m, gp->W2.as<double>(), dq,
                        dmean, dvar);

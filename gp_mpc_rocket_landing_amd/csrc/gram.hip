@@ -198,10 +198,7 @@ static hipError_t launch_gram_rows(hipStream_t s, int kind, const double *a, con
 }
 
 bool gram_rows_tiled(int n1, int d) {
-  static const int rows_env = [] {
-    const char *v = getenv("GPMPC_GRAM_ROWS");
-    return v ? atoi(v) : 1;
-  }();
+  static const int rows_env = gpmpc_env_int("GPMPC_GRAM_ROWS", 1);
   return rows_env && n1 >= 4 * GRAM_ROWS && d >= 11 && d <= 13;
 }
 

@@ -14,6 +14,9 @@ struct gpmpc_ctx {
 };
 
 void gpmpc_set_error(const char *fmt, ...);
+// The one reader of the GPMPC_* switches: atoi of the variable (empty or non-numeric: 0), dflt when
+// unset.  Read once per process: `static const int v = gpmpc_env_int(...)`; per call: a plain call.
+int gpmpc_env_int(const char *name, int dflt);
 // persistent scratch per stream (= per context; slots: 0 trsm block inverses,
 // 1 potrf 32x32 inverses, 2 potrf 128x128 inverses, 3 batched-LML Gram/factor
 // matrices, 4 gp_append temporaries, 5 split-K partials, 7 the Stage device arena; slots 0..7).  Valid until the next call

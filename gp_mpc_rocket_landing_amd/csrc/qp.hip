@@ -312,8 +312,7 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
   // 3-DoF MPC at N = 20 -- when the dynamics rows are equalities, as that solver assumes
   // (GPMPC_QP_FLEET=0: always the generic kernel).  The same OSQP iteration; the block-wide
   // sums and the KKT solve round differently from the generic kernel's.
-  const char *fe = getenv("GPMPC_QP_FLEET");  // (read per call: tests switch it)
-  const bool fleet_env = !fe || atoi(fe);
+  const bool fleet_env = gpmpc_env_int("GPMPC_QP_FLEET", 1) != 0;  // (read per call: tests switch it)
   bool fleet = fleet_env && qp_is_fleet_pattern(n, m, rowptr, colidx);
   for (int64_t r = 0; fleet && r < (int64_t)batch * m; ++r)
     if (r % m < QP_FLEET_MD && l[r] != u[r]) fleet = false;
@@ -336,7 +335,7 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
   double *dob = sg.out(obj, B);
   GPMPC_HIP(sg.upload());
   // GPMPC_QP_STAMPS=1: problem 0's phase cycles (s_memtime) to stderr, a diagnostic
-  static const bool stamp = getenv("GPMPC_QP_STAMPS") && atoi(getenv("GPMPC_QP_STAMPS"));
+  static const int stamp = gpmpc_env_int("GPMPC_QP_STAMPS", 0);
   DevBuf dts;
   if (stamp) {
     GPMPC_HIP(dts.alloc(s, 16 * sizeof(unsigned long long)));

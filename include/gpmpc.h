@@ -152,6 +152,33 @@ enum { GPMPC_GEMM_GRID_2D = 0, GPMPC_GEMM_GRID_TRI = 1, GPMPC_GEMM_GRID_XCD_BATC
 int gpmpc_gemm_diag(gpmpc_ctx *ctx, int op, int M, int N, int K, int batch, const double *A, int64_t lda,
                     int64_t sA, const double *B, int64_t ldb, int64_t sB, double *C, int64_t ldc, int64_t sC,
                     double *D, int64_t ldd, double alpha, double beta, int flags, int p0, int p1, int *path);
+/* diagnostic (tests only), no device: the rows of the SUMSQ partial buffer that the
+ * posterior's consumers sum for an M x N x K product, and in *kind (may be NULL) the kernel
+ * the launcher picks for it (0 64-row tiles, 1 128-row tiles, 2 the K split, 64-row tiles),
+ * both under this process's GPMPC_GEMM128 / GPMPC_GEMM128_KMIN / GPMPC_SPLITK. */
+int gpmpc_gemm_row_tiles(int M, int N, int K, int *kind);
+/* diagnostic (tests only): the launches gpmpc_potrf_batched_dev would make for (n, batch),
+ * without touching a device (no context).
+ * policy: NULL = this process's switches; else GPMPC_POTRF_POLICY_N ints in the order p128,
+ * persist, lat, sweep, trsm, pk, ob, ksplit, fuse, la, syrk_diag, fuse_min, stamps
+ * (csrc/potrf_plan.h PotrfPolicy: the GPMPC_* switch of each and its "auto" value), so a
+ * test sets a switch without mutating the environment of a process that has already cached
+ * it.  form: 0 = 32-column, 1 = persistent, 2 =
+ * 128-column (steps filled only for 2).  Each step is GPMPC_POTRF_STEP_INTS ints: kind
+ * (GPMPC_POTRF_*), c (its first column; of a TRAIL_*, the first trailing column), K0 (the
+ * outer panel's first column) and four operands:
+ *   DIAG            w, packed layout, mode = sweep | (TRSM-form blocks ? 2 : 0), Linv written
+ *   UPD_SYRK_DIAG   w, K, ks            UPD_ROWBLOCK   rows, w, K, ks
+ *   UPDSOLVE        below, K, wn        PSOLVE_*       rows
+ *   TRAIL_*         M, K
+ * Returns the number of steps (may exceed cap; only cap are written), or -2 for a refused
+ * argument. */
+#define GPMPC_POTRF_POLICY_N 13
+#define GPMPC_POTRF_STEP_INTS 7
+enum { GPMPC_POTRF_DIAG = 0, GPMPC_POTRF_UPD_SYRK_DIAG = 1, GPMPC_POTRF_UPD_ROWBLOCK = 2, GPMPC_POTRF_UPDSOLVE = 3,
+       GPMPC_POTRF_PSOLVE_TRSM = 4, GPMPC_POTRF_PSOLVE_LAT = 5, GPMPC_POTRF_PSOLVE_ROWBLOCK = 6,
+       GPMPC_POTRF_TRAIL_LAT = 7, GPMPC_POTRF_TRAIL_SYRK = 8 };
+int gpmpc_potrf_plan(int n, int batch, const int *policy, int *form, int *steps, int cap);
 
 /* ---- a4-a6: exact GP ------------------------------------------------------
  * MultiOutputExactGP.fit (exact_gp.py:476-499 -> ExactGP.fit :118-184) for
