@@ -166,6 +166,7 @@ _sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64,
      ctypes.c_double, ctypes.c_double, _c, _c, _c, _ip)
 _sig("gpmpc_gemm_row_tiles", _c, _c, _c, _c, _ip)
 _sig("gpmpc_potrf_plan", _c, _c, _c, _ip, _ip, _ip, _c)
+_sig("gpmpc_gram_path", _c, _c, _c, _c)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
 _sig("gpmpc_fleet_mc_detach", _c, _vp)
@@ -211,7 +212,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
-            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan"]
+            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path"]
 
 
 class HIPError(RuntimeError):
@@ -886,6 +887,19 @@ def gemm_row_tiles(M, N, K):
     M x N x K product under this process's switches (gpmpc_gemm_row_tiles; no device)."""
     kind = ctypes.c_int(-9)
     return _L.gpmpc_gemm_row_tiles(int(M), int(N), int(K), ctypes.byref(kind)), kind.value
+
+
+GRAM_PATH_ROWS = 64   # gpmpc.h GPMPC_GRAM_PATH_ROWS
+
+
+def gram_path(n1, d, transpose_out=0):
+    """(kernel, D) the Gram launcher takes for n1 rows of d features under this process's
+    switches (gpmpc_gram_path; no device): ("k_gram", D) or ("k_gram_rows", D), D = the
+    width the kernel is instantiated for (0: the one that reads the width at run time)."""
+    p = _L.gpmpc_gram_path(int(n1), int(d), int(transpose_out))
+    if p < 0:
+        _err(p, "gram_path")
+    return ("k_gram_rows" if p & GRAM_PATH_ROWS else "k_gram"), p & ~GRAM_PATH_ROWS
 
 
 # ---- diagnostic: the batched Cholesky's launch plan (gpmpc_potrf_plan; no device) ----

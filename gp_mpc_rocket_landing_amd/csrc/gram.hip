@@ -45,7 +45,8 @@ __global__ __launch_bounds__(256) void k_gram(int kind, const double *__restrict
                                               const double *__restrict__ nb, int n2, int d,
                                               double sigma2, double iso_scale,
                                               double *__restrict__ K, int64_t ldk, int tr) {
-  __shared__ double sa[GRAM_TILE][D + 1];
+  // (the runtime-width instantiation D = 0 serves every d <= GRAM_MAXD: its rows are that wide)
+  __shared__ double sa[GRAM_TILE][((D > 0) ? D : GRAM_MAXD) + 1];
   __shared__ double sna[GRAM_TILE];
   const int r0 = blockIdx.y * GRAM_TILE, c0 = blockIdx.x * GRAM_TILE;
   const int tid = threadIdx.x;
@@ -202,13 +203,27 @@ bool gram_rows_tiled(int n1, int d) {
   return rows_env && n1 >= 4 * GRAM_ROWS && d >= 11 && d <= 13;
 }
 
+// The kernel launch_gram takes for a shape: the width k_gram is instantiated for (0: the
+// runtime-width instantiation), with GPMPC_GRAM_PATH_ROWS the same of k_gram_rows.
+static int gram_path(int n1, int d, int transpose_out) {
+  const int D = (d >= 11 && d <= 13) ? d : 0;
+  return (!transpose_out && gram_rows_tiled(n1, d)) ? (GPMPC_GRAM_PATH_ROWS | D) : D;
+}
+
+// diagnostic, no device: gram_path under this process's GPMPC_GRAM_ROWS
+extern "C" int gpmpc_gram_path(int n1, int d, int transpose_out) {
+  GPMPC_CHECK_ARG(n1 >= 0 && d >= 1 && d <= GRAM_MAXD);
+  return gram_path(n1, d, transpose_out);
+}
+
 hipError_t launch_gram(hipStream_t s, int kind, const double *a, const double *na, int n1,
                        const double *b, const double *nb, int n2, int d, double sigma2,
                        double iso_scale, double *K, int64_t ldk, int transpose_out,
                        const FleetPlans *plans) {
   if (n1 <= 0 || n2 <= 0) return hipSuccess;
   if (d > GRAM_MAXD) return hipErrorInvalidValue;
-  const bool rows = !transpose_out && gram_rows_tiled(n1, d);
+  const int path = gram_path(n1, d, transpose_out);
+  const bool rows = (path & GPMPC_GRAM_PATH_ROWS) != 0;
   if (plans && !(rows && d == 11)) return hipErrorInvalidValue;  // only k_gram_rows<11> forms the rows
   if (rows) {
     if (d == 11) return launch_gram_rows<11>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk, plans);
@@ -216,7 +231,7 @@ hipError_t launch_gram(hipStream_t s, int kind, const double *a, const double *n
     return launch_gram_rows<13>(s, kind, a, na, n1, b, nb, n2, sigma2, iso_scale, K, ldk, nullptr);
   }
   dim3 g((n2 + GRAM_TILE - 1) / GRAM_TILE, (n1 + GRAM_TILE - 1) / GRAM_TILE);
-  switch (d) {
+  switch (path) {
     case 11:
       hipLaunchKernelGGL(k_gram<11>, g, dim3(256), 0, s, kind, a, na, n1, b, nb, n2, d, sigma2,
                          iso_scale, K, ldk, transpose_out);

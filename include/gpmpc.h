@@ -90,6 +90,14 @@ int gpmpc_gram(gpmpc_ctx *ctx, int kind, const double *X1, int n1, const double 
  * Matern kernels define). */
 int gpmpc_gram_grad(gpmpc_ctx *ctx, int kind, const double *X1, int n1, const double *X2, int n2,
                     int d, const double *ls, double sigma2, double *K, double *G);
+/* diagnostic (tests only), no device: the kernel the Gram launcher takes for n1 rows of d
+ * features under this process's GPMPC_GRAM_ROWS (the launcher itself branches on this
+ * value).  Returns D, the width k_gram is instantiated for (11, 12, 13, or 0: the
+ * instantiation that reads the width at run time), or GPMPC_GRAM_PATH_ROWS | D for the
+ * row-tiled k_gram_rows<D>; transpose_out != 0 always takes k_gram.  -2 for d outside
+ * 1..32 or n1 < 0. */
+enum { GPMPC_GRAM_PATH_ROWS = 64 };
+int gpmpc_gram_path(int n1, int d, int transpose_out);
 
 /* ---- Cholesky factor / solve -------------------------------------------
  * Replaces np.linalg.cholesky (exact_gp.py:164,170; sparse_gp.py:187,205).
