@@ -342,7 +342,7 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
     GPMPC_HIP(hipMemsetAsync(dts.p, 0, 16 * sizeof(unsigned long long), s));
   }
   if (fleet) {
-    GPMPC_HIP((batch <= qp_cu_count(ctx->device) ? launch_qp_fleet_wide : launch_qp_fleet_narrow)(
+    GPMPC_HIP((batch <= qp_cu_count(ctx->device) ? fq_wide::launch_qp : fq_narrow::launch_qp)(
         s, batch, pat->dev, to_dev(*st), dA, dP, dq, dl, du, dx0, drho, dy0, dxo, dyo, dit, dst, dob));
   } else {
     GPMPC_HIP(launch_qp_batched(s, pat->dev, to_dev(*st), batch, dA, dP, dq, dl, du, dx0, drho, dy0, dxo, dyo,

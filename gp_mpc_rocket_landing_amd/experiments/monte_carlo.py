@@ -258,7 +258,8 @@ def _same(a, b) -> bool:
         return False
 
 
-# what k_fleet_control's QP assembly compiles in (csrc/fleet.hip), against mpc/qp_builder.py
+# what the control kernels' QP assembly compiles in (k_fleet_control in csrc/fleet.hip,
+# k_fleet_control2 and fleet_box in csrc/fleet_control.h), against mpc/qp_builder.py
 _FLEET_QP = dict(Q_DIAG=[0.0, 10.0, 10.0, 10.0, 1.0, 1.0, 1.0], R_DIAG=[0.01, 0.01, 0.01], QF_SCALE=10.0,
                  X_MIN=[-np.inf, -100.0, -100.0, -100.0, -50.0, -50.0, -50.0],
                  X_MAX=[np.inf, 500.0, 100.0, 100.0, 50.0, 50.0, 50.0],
@@ -414,7 +415,7 @@ class MonteCarloSimulator:
         """(fleet keyword arguments, GP device handle) when this simulator is exactly what
         the device fleet restates, else (None, reason).  Host logic only: no device call.
 
-        The fleet compiles in (csrc/fleet.hip): the Simple3DoF features with v_ref 10,
+        The fleet compiles in (csrc/fleet_control.h, csrc/fleet.hip): the Simple3DoF features with v_ref 10,
         altitude and density on and the default atmosphere (features3); the Euler plant
         with alpha = 1/30, g = [-1, 0, 0] (plant_euler); the solve protocol with the
         incremental target; and k_fleet_control's QP -- Q = diag(0, 10, 10, 10, 1, 1, 1),

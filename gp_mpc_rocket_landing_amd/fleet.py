@@ -4,7 +4,8 @@ The fleet is the batched form of ``MonteCarloSimulator.run_single``
 (monte_carlo.py:401-583) driving the 3-DoF ``GPMPC`` surface: every control
 step runs the GP posterior at the N horizon points of every landing, the RTI
 QP assembly with the GP mean, the batched OSQP-style ADMM, the plant step and
-the termination rules -- all on the GPU (libgpmpc_hip.so, csrc/fleet.hip).
+the termination rules -- all on the GPU (libgpmpc_hip.so: csrc/fleet.hip, the
+control step's protocol and kernels in csrc/fleet_control.h).
 """
 from __future__ import annotations
 
