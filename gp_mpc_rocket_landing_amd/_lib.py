@@ -166,6 +166,7 @@ _sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64,
      ctypes.c_double, ctypes.c_double, _c, _c, _c, _ip)
 _sig("gpmpc_gemm_row_tiles", _c, _c, _c, _c, _ip)
 _sig("gpmpc_potrf_plan", _c, _c, _c, _ip, _ip, _ip, _c)
+_sig("gpmpc_gemm_plan", _c, _c, _c, _c, _c, _c, ctypes.c_double, _c, _c, _c, _ip, _ip)
 _sig("gpmpc_gram_path", _c, _c, _c, _c)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
 _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
@@ -212,7 +213,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
-            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path"]
+            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan"]
 
 
 class HIPError(RuntimeError):
@@ -765,6 +766,7 @@ def select_diverse(ctx, X, scores, n_select, diversity_weight=0.5, path=0):
 GEMM_OP = {"nt": 0, "nn": 1, "nn_batched": 2, "tn": 3, "rowblock": 4, "lat0": 5, "lat1": 6, "syrk_diag": 7,
            "updsolve": 8, "sumsq": 9, "sumsq_mean": 10}
 GEMM_TRI_A, GEMM_LOWER_C, GEMM_TRI_B = 1, 2, 4
+GEMM_NO_SCRATCH = 8   # gemm_plan only: the plan when the split-K partial buffer is not to be had
 GEMM_PATH = {-1: "none", 0: "64", 1: "128", 2: "128_ksplit", 3: "streamk", 4: "splitk", 5: "lat", 6: "syrk_diag",
              7: "updsolve"}
 GEMM_GRID = {0: "2d", 1: "tri", 2: "xcd_batch", 3: "rowblock_xcd"}
@@ -887,6 +889,30 @@ def gemm_row_tiles(M, N, K):
     M x N x K product under this process's switches (gpmpc_gemm_row_tiles; no device)."""
     kind = ctypes.c_int(-9)
     return _L.gpmpc_gemm_row_tiles(int(M), int(N), int(K), ctypes.byref(kind)), kind.value
+
+
+# csrc/gemm_plan.h: GemmPolicy's fields with their defaults ("auto" for the three-state ones)
+GEMM_POLICY = {"big": 1, "kmin": 256, "splitk": 1, "syrk128": -1, "streamk": -1, "ksplit": 0, "remap": 0,
+               "xcd_batch": 1, "rowblock_xcd": 1, "post_xcd": 0}
+
+
+def gemm_plan(op, M, N, K, batch=1, beta=0.0, flags=0, p0=0, p1=0, **switches):
+    """What the launcher of ``op`` (a GEMM_OP name with a decision: nt, nn, nn_batched, tn,
+    rowblock, sumsq, sumsq_mean) does for the product (gpmpc_gemm_plan; no device):
+    (path, split, grid) as gemm_diag reports them, then the launch grid (gx, gy, gz), the tile
+    height and the skinny splits' chunk length kc.  Without keywords the plan follows this
+    process's GPMPC_* switches; with any, the default policy with those fields of GEMM_POLICY
+    replaced."""
+    unknown = set(switches) - set(GEMM_POLICY)
+    if unknown:
+        raise TypeError(f"gemm_plan: unknown switches {sorted(unknown)}")
+    pol = np.array(list(dict(GEMM_POLICY, **switches).values()), np.int32)
+    out = np.full(8, -9, np.int32)
+    opc = GEMM_OP[op] if isinstance(op, str) else int(op)
+    _chk(_L.gpmpc_gemm_plan(opc, int(M), int(N), int(K), int(batch), float(beta), int(flags), int(p0), int(p1),
+                            _i(pol) if switches else None, _i(out)), "gemm_plan")
+    return (GEMM_PATH[int(out[0])], int(out[1]), GEMM_GRID[int(out[2])], (int(out[3]), int(out[4]), int(out[5])),
+            int(out[6]), int(out[7]))
 
 
 GRAM_PATH_ROWS = 64   # gpmpc.h GPMPC_GRAM_PATH_ROWS

@@ -17,12 +17,13 @@
 #include "internal.h"
 #include "mfma64.h"
 #include "gemm.h"
+#include "gemm_plan.h"
 
 #define GT 64
 #define GK 16
 
 // The kernel path, K split and grid mapping of this thread's last launch_* call, recorded
-// where the kernel is launched (gpmpc_gemm_diag reports them; the values are
+// once per launcher from the plan it executed (gpmpc_gemm_diag reports them; the values are
 // GPMPC_GEMM_PATH_* / GPMPC_GEMM_GRID_* of gpmpc.h).
 enum { PATH_NONE = -1, PATH_64 = 0, PATH_128 = 1, PATH_128_KSPLIT = 2, PATH_STREAMK = 3, PATH_SPLITK = 4,
        PATH_LAT = 5, PATH_SYRK_DIAG = 6, PATH_UPDSOLVE = 7 };
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt(int M, int N, int K, const doub
   A += bz * sA_;
   B += bz * sB_;
   C += bz * sC_;
-  // optional XCD-aware order (1-D grid, GPMPC_GEMM_REMAP=1): workgroup i runs
+  // optional XCD-aware order (1-D grid, the policy's remap): workgroup i runs
   // on XCD i % 8; each XCD gets whole column blocks and walks their row tiles
   // back to back.  Off by default: for the posterior GEMM the plain order
   // (concurrent workgroups share a W row block, K* streams from the 256 MB
@@ -259,9 +260,6 @@ __global__ __launch_bounds__(256) void k_gemm_nt(int M, int N, int K, const doub
   }
 }
 
-// GPMPC_POST_XCD=1: the posterior GEMM's column-grouped XCD mapping (k_gemm128, tri_grid 2)
-static int post_xcd() { static const int v = gpmpc_env_int("GPMPC_POST_XCD", 0); return v; }
-
 // ---------------------------------------------------------------------------
 // Large-tile variant: 128 x 128 per workgroup, each wave a 64 x 64 quadrant
 // (4 x 4 MFMA blocks: 8 fragment reads feed 16 MFMAs), K staged 16 at a time,
@@ -269,6 +267,8 @@ static int post_xcd() { static const int v = gpmpc_env_int("GPMPC_POST_XCD", 0);
 // 16-double row segment).  Row tiles are dispatched longest-first when A is
 // triangular.  Used when both M and N are large (posterior GEMM, trailing SYRK).
 #include "mma128.h"
+static_assert(GEMM_GT == GT && GEMM_GK == GK && GEMM_BT == BT && GEMM_SUMSQ_128 == 1 && GEMM_SUMSQ_SPLITK == 2,
+              "gemm_plan.h plans in the kernels' tiles and the SUMSQ kinds of gemm.h");
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void k_gemm128(int M, int N, int K, const double *__restrict__ A,
@@ -944,27 +944,21 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(int M, int N, int S, cons
   }
 }
 
-static bool splitk_env() { static const int v = gpmpc_env_int("GPMPC_SPLITK", 1); return v != 0; }
-
-// form: 0 NT (A M x K, B N x K), 1 NN (B K x N), 2 TN (A K x M, B K x N).  Returns false
-// (nothing launched) when the product is not skinny enough or scratch is unavailable.
-static bool launch_splitk(hipStream_t s, int form, int M, int N, int K, const double *A, int64_t lda,
-                          const double *B, int64_t ldb, double *C, int64_t ldc, double alpha, double beta,
-                          hipError_t &err) {
-  if (!splitk_env() || !(M <= 32 || N <= 32) || K < 256) return false;
-  const int tiles = ((M + GT - 1) / GT) * ((N + GT - 1) / GT);
-  int S = std::max(1, std::min(512 / tiles, K / 64));
-  if (S < 2) return false;
-  const int kc = ((K + S - 1) / S + GK - 1) / GK * GK;
-  S = (K + kc - 1) / kc;
+// The two executors of a plan that says split (PATH_SPLITK: p.split chunks of p.kc along K,
+// gemm_plan.h).  false, nothing launched: scratch slot 5 is not to be had -- the caller plans
+// again without it, the one decision left to run time.
+// form: 0 NT (A M x K, B N x K), 1 NN (B K x N), 2 TN (A K x M, B K x N).
+static bool launch_splitk(hipStream_t s, int form, const GemmPlan &p, int M, int N, int K, const double *A,
+                          int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, double alpha,
+                          double beta) {
+  const int S = p.split, kc = p.kc;
   const int64_t MN = (int64_t)M * N;
   double *P = (double *)gpmpc_scratch(s, 5, sizeof(double) * MN * S);
   if (!P) return false;
   // chunk q: A and B advance by kc along K
   const int64_t sA = form == 2 ? (int64_t)kc * lda : kc, sB = form == 0 ? kc : (int64_t)kc * ldb;
   const int klast = K - (S - 1) * kc;  // the last chunk's length (one launch for all chunks)
-  const dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, S);
-  gemm_path(PATH_SPLITK, S);
+  const dim3 g(p.gx, p.gy, p.gz);
   if (form == 0)
     hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 0, 0>), g, dim3(256), 0, s, M, N, kc, A, lda, B, ldb, P, (int64_t)N,
                        1.0, 0.0, 0, 0, sA, sB, MN, M, nullptr, (int64_t)0, 0, 0, klast);
@@ -976,7 +970,6 @@ static bool launch_splitk(hipStream_t s, int form, int M, int N, int K, const do
                        1.0, 0.0, 0, 0, sA, sB, MN, M, nullptr, (int64_t)0, 0, 0, klast);
   const int rb = (int)std::min<int64_t>((MN + 255) / 256, 1024);
   hipLaunchKernelGGL(k_splitk_reduce, dim3(rb), dim3(256), 0, s, M, N, S, P, C, ldc, alpha, beta);
-  err = hipGetLastError();
   return true;
 }
 
@@ -1015,137 +1008,97 @@ __global__ __launch_bounds__(256) void k_splitk_sumsq(int M, int N, int S, const
   }
 }
 
-static bool launch_splitk_sumsq(hipStream_t s, int M, int N, int K, const double *A, int64_t lda, const double *B,
-                                int64_t ldb, double *part, int64_t ldp, int msum, double *Cm, int64_t ldm,
-                                hipError_t &err) {
-  if (!splitk_env() || N > GT || K < 256) return false;
-  const int ty = (M + GT - 1) / GT;
-  int S = std::max(1, std::min(512 / ty, K / 64));
-  if (S < 2) return false;
-  const int kc = ((K + S - 1) / S + GK - 1) / GK * GK;
-  S = (K + kc - 1) / kc;
+static bool launch_splitk_sumsq(hipStream_t s, const GemmPlan &p, int M, int N, int K, const double *A, int64_t lda,
+                                const double *B, int64_t ldb, double *part, int64_t ldp, int msum, double *Cm,
+                                int64_t ldm) {
+  const int S = p.split, kc = p.kc;
   const int64_t MN = (int64_t)M * N;
   double *P = (double *)gpmpc_scratch(s, 5, sizeof(double) * MN * S);
   if (!P) return false;
-  gemm_path(PATH_SPLITK, S);
-  hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 0, 0>), dim3(1, ty, S), dim3(256), 0, s, M, N, kc, A, lda, B, ldb, P,
-                     (int64_t)N, 1.0, 0.0, 0, 0, (int64_t)kc, (int64_t)kc, MN, M, nullptr, (int64_t)0, 0, 0,
+  hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 0, 0>), dim3(p.gx, p.gy, p.gz), dim3(256), 0, s, M, N, kc, A, lda, B, ldb,
+                     P, (int64_t)N, 1.0, 0.0, 0, 0, (int64_t)kc, (int64_t)kc, MN, M, nullptr, (int64_t)0, 0, 0,
                      K - (S - 1) * kc);
-  hipLaunchKernelGGL(k_splitk_sumsq, dim3(ty, (N + 3) / 4), dim3(256), 0, s, M, N, S, P, msum, part, ldp, Cm, ldm);
-  err = hipGetLastError();
+  hipLaunchKernelGGL(k_splitk_sumsq, dim3(p.gy, (N + 3) / 4), dim3(256), 0, s, M, N, S, P, msum, part, ldp, Cm, ldm);
   return true;
 }
 
-static int gemm_big_env() { static const int v = gpmpc_env_int("GPMPC_GEMM128", 1); return v; }
-
-static int gemm_kmin_env() { static const int v = gpmpc_env_int("GPMPC_GEMM128_KMIN", 2 * BT); return v; }
-
 // The kernel launch_gemm_sumsq_mean picks for an (M x K) [W; alpha^T] against N query
-// rows (batch 1, triangular A): the rules of launch_gemm_impl below.  A caller whose column
-// count shrinks over time (the fleet's running prefix) fixes this at its planned size and
-// passes it back, so every column sees the same kernel, hence the same bits.
+// rows (batch 1, triangular A): the plan's answer for that request under this process's
+// switches (no columns plan as one: the rules hold N against lower bounds only).  A caller
+// whose column count shrinks over time (the fleet's running prefix) fixes this at its planned
+// size and passes it back, so every column sees the same kernel, hence the same bits.
 int gemm_sumsq_kind(int M, int N, int K) {
-  if (gemm_big_env() && M >= 2 * BT && N >= 2 * BT && K >= gemm_kmin_env()) return GEMM_SUMSQ_128;
-  if (splitk_env() && N <= GT && K >= 256 && std::max(1, std::min(512 / ((M + GT - 1) / GT), K / 64)) >= 2)
-    return GEMM_SUMSQ_SPLITK;
-  return GEMM_SUMSQ_64;
+  const GemmPlan p = gemm_plan(gemm_policy_env(), {GPMPC_GEMM_OP_SUMSQ, M, std::max(N, 1), K, 1, false, 1, 0});
+  return p.path == PATH_128 ? GEMM_SUMSQ_128 : p.path == PATH_SPLITK ? GEMM_SUMSQ_SPLITK : GEMM_SUMSQ_64;
 }
 
+// launch_gemm_nt and the SUMSQ launchers: plan (gemm_plan.h), then launch with the plan's numbers
 static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, const double *A,
                                    int64_t lda, const double *B, int64_t ldb, double *C,
                                    int64_t ldc, double alpha, double beta, int tri_a, int lower_c,
                                    int batch, int64_t sA, int64_t sB, int64_t sC, int msum,
                                    double *Cm, int64_t ldm, int kind = -1) {
-  if (M <= 0 || N <= 0) return hipSuccess;
-  const int big_env = gemm_big_env();
-  // kind >= 0 (EPI_SUMSQ, batch 1): that kernel, whatever the size (gemm_sumsq_kind)
-  if (epi != EPI_SUMSQ || batch != 1) kind = -1;
-  const bool tg = lower_c && M == N && !tri_a;
-  // a lower-triangular batch takes 128-tiles only when they fill >= 2 rounds
-  // of 512 resident workgroups or K is long enough to split; otherwise they
-  // quantise badly (1.1-1.25 rounds: 21-36% vs 44-50% for 64-tiles).  FITC
-  // 2000 x 4000: 128-tiles + split-K 56% vs 39%
-  const int t128 = ((M + BT - 1) / BT) * ((M + BT - 1) / BT + 1) / 2 * batch;
-  static const int syrk128_env = gpmpc_env_int("GPMPC_SYRK128", -1);
-  const bool tri_ok = !tg || (syrk128_env >= 0 ? syrk128_env != 0 : t128 >= 1024 || K >= 1024);
-  static const int sk_env = gpmpc_env_int("GPMPC_STREAMK", -1);
-  // stream-K for long accumulations into C on big tiles: measured 2000^2 x 4000
-  // 60% (split-K 55%), 4000^2 x 4000 72%, 16 x 1000^2 x 1000 56% (64-tiles 52%);
-  // smaller or shorter products (n ~ 500, K <= 256) keep the tiled kernels
-  const bool sk_ok = epi == EPI_STORE && beta == 1.0 && !tri_a && M >= 2 * BT && N >= 2 * BT &&
-                     K >= 2 * BT;
-  const bool sk_auto = M >= 768 && N >= 768 && K >= 512;
-  if (sk_ok && (sk_env >= 0 ? sk_env > 0 : sk_auto)) {
-    const int tx = (N + BT - 1) / BT, ty = (M + BT - 1) / BT;
-    const int T = tg ? ty * (ty + 1) / 2 : tx * ty;
-    const int64_t total = (int64_t)T * batch * ((K + GK - 1) / GK);
-    const int nwg = (int)std::min<int64_t>(512, total);
-    gemm_path(PATH_STREAMK, nwg, tg ? GRID_TRI : GRID_2D);
-    hipLaunchKernelGGL(k_gemm128_sk, dim3(nwg), dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                       alpha, (int)tg, tx, T, sA, sB, sC, total);
-    return hipGetLastError();
+  GemmRequest r{epi == EPI_SUMSQ ? GPMPC_GEMM_OP_SUMSQ : GPMPC_GEMM_OP_NT, M, N, K, batch, beta == 1.0, tri_a,
+                lower_c, kind};
+  GemmPlan p = gemm_plan(gemm_policy_env(), r);
+  if (p.path == PATH_SPLITK &&
+      !(epi == EPI_STORE ? launch_splitk(s, 0, p, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta)
+                         : launch_splitk_sumsq(s, p, M, N, K, A, lda, B, ldb, C, ldc, msum, Cm, ldm))) {
+    r.no_scratch = true;
+    p = gemm_plan(gemm_policy_env(), r);
   }
-  const int kmin_env = gemm_kmin_env();
-  const bool use128 = kind >= 0 ? kind == GEMM_SUMSQ_128 : big_env && tri_ok && M >= 2 * BT && N >= 2 * BT && K >= kmin_env;
-  if (use128) {
-    const int tx = (N + BT - 1) / BT, ty = (M + BT - 1) / BT;
-    // split K when the tiles cannot give each CU ~4 workgroups to interleave (STORE
-    // with beta = 1: partial products are added atomically); >= 512 of K per split
-    const int tiles = (lower_c ? ty * (ty + 1) / 2 : tx * ty) * batch;
-    // cost model: rounds of 512 resident workgroups (2 per CU) x (K per split
-    // + ~256 of fixed cost: prologue, atomic C update).  Measured on 2000^2 x
-    // 4000: ks 1/2/3/4/6/8 -> 30/38/53/43/49/45% (ks 4 leaves a 32-WG tail)
-    int ksplit = 1;
-    if (epi == EPI_STORE && beta == 1.0 && K >= 1024) {
-      double best = 1e30;
-      for (int ks = 1; ks <= K / 256 && ks <= 16; ++ks) {
-        const double c = (double)((tiles * ks + 511) / 512) * ((double)K / ks + 256.0);
-        if (c < best * 0.98) best = c, ksplit = ks;
-      }
-    }
-    static const int ks_env = gpmpc_env_int("GPMPC_KSPLIT", 0);
-    if (ks_env > 0 && epi == EPI_STORE && beta == 1.0) ksplit = ks_env;
-    // lower-triangular square products launch only their lower tiles, in a
-    // 1-D order that interleaves them over the 8 XCDs (a 2-D grid whose
-    // column count is a multiple of 8 pins columns to XCDs: 8x imbalance)
-    dim3 g(tg ? ty * (ty + 1) / 2 : tx, tg ? 1 : ty, batch * ksplit);
-    gemm_path(ksplit > 1 ? PATH_128_KSPLIT : PATH_128, ksplit, tg ? GRID_TRI : GRID_2D);
-    if (epi == EPI_STORE)
-      hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                         alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, ksplit,
-                         (int)tg);
-    else
-      hipLaunchKernelGGL(k_gemm128<EPI_SUMSQ>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                         alpha, beta, tri_a, 0, sA, sB, sC, msum, Cm, ldm, 1,
-                         (post_xcd() && batch == 1 && tx % 8 == 0) ? 2 : 0);
-    return hipGetLastError();
+  gemm_path(p.path, p.split, p.grid);
+  const dim3 g(p.gx, p.gy, p.gz);
+  switch (p.path) {
+    case PATH_NONE:
+      return hipSuccess;
+    case PATH_SPLITK:  // launched above
+      break;
+    case PATH_STREAMK:
+      hipLaunchKernelGGL(k_gemm128_sk, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, alpha, p.tg, p.tx, p.T,
+                         sA, sB, sC, p.total);
+      break;
+    case PATH_128:
+    case PATH_128_KSPLIT:
+      if (epi == EPI_STORE)
+        hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
+                           alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, p.split, p.tg);
+      else
+        hipLaunchKernelGGL(k_gemm128<EPI_SUMSQ>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
+                           alpha, beta, tri_a, 0, sA, sB, sC, msum, Cm, ldm, 1, p.tg);
+      break;
+    default:  // PATH_64
+      if (epi == EPI_STORE)
+        hipLaunchKernelGGL(k_gemm_nt<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
+                           alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, p.rt, p.xb, 0);
+      else
+        hipLaunchKernelGGL(k_gemm_nt<EPI_SUMSQ>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
+                           alpha, beta, tri_a, 0, sA, sB, sC, msum, Cm, ldm, p.rt, 0, 0);
   }
-  if (epi == EPI_STORE && batch == 1 && !tri_a && !lower_c) {
-    hipError_t e = hipSuccess;
-    if (launch_splitk(s, 0, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
+  return hipGetLastError();
+}
+
+// The products with a k-major operand on the 64-tile kernel: NN (B K x N), TN (A K x M too),
+// NN_BATCHED (op: their GPMPC_GEMM_OP_*)
+static hipError_t launch_gemm_kmajor(hipStream_t s, int op, int M, int N, int K, const double *A, int64_t lda,
+                                     int64_t sA, const double *B, int64_t ldb, int64_t sB, double *C, int64_t ldc,
+                                     int64_t sC, double alpha, double beta, int batch) {
+  const bool tn = op == GPMPC_GEMM_OP_TN;
+  GemmRequest r{op, M, N, K, batch, beta == 1.0, 0, 0};
+  GemmPlan p = gemm_plan(gemm_policy_env(), r);
+  if (p.path == PATH_SPLITK && !launch_splitk(s, tn ? 2 : 1, p, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta)) {
+    r.no_scratch = true;
+    p = gemm_plan(gemm_policy_env(), r);
   }
-  if (epi == EPI_SUMSQ && batch == 1 &&
-      (kind >= 0 ? kind == GEMM_SUMSQ_SPLITK : gemm_sumsq_kind(M, N, K) != GEMM_SUMSQ_128)) {
-    hipError_t e = hipSuccess;  // (a triangular A's zero chunks are multiplied: the split is latency work)
-    if (launch_splitk_sumsq(s, M, N, K, A, lda, B, ldb, C, ldc, msum, Cm, ldm, e)) return e;
-  }
-  const int tx = (N + GT - 1) / GT, ty = (M + GT - 1) / GT;
-  // (off: measured slower for the posterior GEMM, W blocks thrash)
-  static const int remap_env = gpmpc_env_int("GPMPC_GEMM_REMAP", 0);
-  const bool remap = remap_env && batch == 1 && ty > 1 && tx % 8 == 0;
-  static const int xb_env = gpmpc_env_int("GPMPC_XCD_BATCH", 1);
-  const int T = ty * (ty + 1) / 2;
-  const int xb = (tg && xb_env && batch >= 8) ? batch : 0;
-  dim3 g = xb ? dim3(T * ((batch + 7) / 8) * 8, 1, 1)
-         : tg ? dim3(T, 1, batch) : remap ? dim3(tx * ty, 1, 1) : dim3(tx, ty, batch);
-  const int rt = tg ? -1 : remap ? ty : 0;
-  gemm_path(PATH_64, 1, xb ? GRID_XCD_BATCH : tg ? GRID_TRI : GRID_2D);
-  if (epi == EPI_STORE)
-    hipLaunchKernelGGL(k_gemm_nt<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                       alpha, beta, tri_a, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, rt, xb, 0);
-  else
-    hipLaunchKernelGGL(k_gemm_nt<EPI_SUMSQ>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                       alpha, beta, tri_a, 0, sA, sB, sC, msum, Cm, ldm, rt, 0, 0);
+  gemm_path(p.path, p.split, p.grid);
+  if (p.path == PATH_NONE) return hipSuccess;
+  const dim3 g(p.gx, p.gy, p.gz);
+  if (p.path == PATH_64 && tn)
+    hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 1>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
+                       ldc, alpha, beta, 0, 0, sA, sB, sC, M, nullptr, (int64_t)0, 0, 0, 0);
+  else if (p.path == PATH_64)  // (PATH_SPLITK: launched above)
+    hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 0>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
+                       ldc, alpha, beta, 0, 0, sA, sB, sC, M, nullptr, (int64_t)0, 0, 0, 0);
   return hipGetLastError();
 }
 
@@ -1153,42 +1106,22 @@ static hipError_t launch_gemm_impl(hipStream_t s, int epi, int M, int N, int K, 
 hipError_t launch_gemm_nn(hipStream_t s, int M, int N, int K, const double *A, int64_t lda,
                           const double *B, int64_t ldb, double *C, int64_t ldc, double alpha,
                           double beta) {
-  if (M <= 0 || N <= 0) return hipSuccess;
-  hipError_t e = hipSuccess;
-  if (launch_splitk(s, 1, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
-  dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, 1);
-  gemm_path(PATH_64);
-  hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 0>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
-                     ldc, alpha, beta, 0, 0, (int64_t)0, (int64_t)0, (int64_t)0, M, nullptr,
-                     (int64_t)0, 0, 0, 0);
-  return hipGetLastError();
+  return launch_gemm_kmajor(s, GPMPC_GEMM_OP_NN, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, 0, alpha, beta, 1);
 }
 
 // the same for batch products sA / sB / sC elements apart
 hipError_t launch_gemm_nn_batched(hipStream_t s, int M, int N, int K, const double *A, int64_t lda, int64_t sA,
                                   const double *B, int64_t ldb, int64_t sB, double *C, int64_t ldc, int64_t sC,
                                   double alpha, double beta, int batch) {
-  if (M <= 0 || N <= 0 || batch <= 0) return hipSuccess;
-  dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, batch);
-  gemm_path(PATH_64);
-  hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 0>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
-                     ldc, alpha, beta, 0, 0, sA, sB, sC, M, nullptr, (int64_t)0, 0, 0, 0);
-  return hipGetLastError();
+  return launch_gemm_kmajor(s, GPMPC_GEMM_OP_NN_BATCHED, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, alpha, beta,
+                            batch);
 }
 
 // C (M x N) = alpha A^T B + beta C with A (K x M) and B (K x N) row-major ("TN")
 hipError_t launch_gemm_tn(hipStream_t s, int M, int N, int K, const double *A, int64_t lda,
                           const double *B, int64_t ldb, double *C, int64_t ldc, double alpha,
                           double beta) {
-  if (M <= 0 || N <= 0) return hipSuccess;
-  hipError_t e = hipSuccess;
-  if (launch_splitk(s, 2, M, N, K, A, lda, B, ldb, C, ldc, alpha, beta, e)) return e;
-  dim3 g((N + GT - 1) / GT, (M + GT - 1) / GT, 1);
-  gemm_path(PATH_64);
-  hipLaunchKernelGGL((k_gemm_nt<EPI_STORE, 1, 1>), g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C,
-                     ldc, alpha, beta, 0, 0, (int64_t)0, (int64_t)0, (int64_t)0, M, nullptr,
-                     (int64_t)0, 0, 0, 0);
-  return hipGetLastError();
+  return launch_gemm_kmajor(s, GPMPC_GEMM_OP_TN, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, 0, alpha, beta, 1);
 }
 
 // C = alpha A B^T + beta C with N <= 128 on the 128 x 128 tile kernel: one
@@ -1198,17 +1131,13 @@ hipError_t launch_gemm_nt_rowblock(hipStream_t s, int M, int N, int K, const dou
                                    int64_t lda, const double *B, int64_t ldb, double *C,
                                    int64_t ldc, double alpha, double beta, int batch, int64_t sA,
                                    int64_t sB, int64_t sC, int lower_c, int ksplit) {
-  if (M <= 0 || N <= 0) return hipSuccess;
-  if (N > BT) return hipErrorInvalidValue;
-  // split K (partial products added atomically): only with beta = 1 and C apart from A, B
-  if (ksplit < 1 || beta != 1.0) ksplit = 1;
-  dim3 g(1, (M + BT - 1) / BT, batch * ksplit);
-  // a batch of >= 8 matrices (a multiple of 8): each matrix's row tiles on one XCD
-  static const int xb_env = gpmpc_env_int("GPMPC_ROWBLOCK_XCD", 1);
-  const int tg = (xb_env && batch >= 8 && batch % 8 == 0) ? 3 : 0;
-  gemm_path(ksplit > 1 ? PATH_128_KSPLIT : PATH_128, ksplit, tg ? GRID_ROWBLOCK_XCD : GRID_2D);
-  hipLaunchKernelGGL(k_gemm128<EPI_STORE>, g, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
-                     alpha, beta, 0, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, ksplit, tg);
+  if (M > 0 && N > BT) return hipErrorInvalidValue;
+  const GemmPlan p = gemm_plan(gemm_policy_env(),
+                               {GPMPC_GEMM_OP_ROWBLOCK, M, N, K, batch, beta == 1.0, 0, lower_c, -1, ksplit});
+  gemm_path(p.path, p.split, p.grid);
+  if (p.path == PATH_NONE) return hipSuccess;
+  hipLaunchKernelGGL(k_gemm128<EPI_STORE>, dim3(p.gx, p.gy, p.gz), dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc,
+                     alpha, beta, 0, lower_c, sA, sB, sC, M, nullptr, (int64_t)0, p.split, p.tg);
   return hipGetLastError();
 }
 
@@ -1238,6 +1167,31 @@ hipError_t launch_gemm_sumsq_mean(hipStream_t s, int n, int n_out, int P, const 
 extern "C" int gpmpc_gemm_row_tiles(int M, int N, int K, int *kind) {
   if (kind) *kind = gemm_sumsq_kind(M, N, K);
   return gemm_row_tiles(M, N, K);
+}
+
+// diagnostic, no device: the plan the launcher of op would execute (gpmpc.h)
+static_assert(sizeof(GemmPolicy) == GPMPC_GEMM_POLICY_N * sizeof(int) &&
+              offsetof(GemmPlan, kc) == (GPMPC_GEMM_PLAN_INTS - 1) * sizeof(int), "gpmpc_gemm_plan's layouts");
+extern "C" int gpmpc_gemm_plan(int op, int M, int N, int K, int batch, double beta, int flags, int p0, int p1,
+                               const int *policy, int *plan) {
+  GPMPC_CHECK_ARG(plan && M >= 0 && N >= 0 && K >= 0 && batch >= 1 && (flags & ~15) == 0);
+  const bool sumsq = op == GPMPC_GEMM_OP_SUMSQ || op == GPMPC_GEMM_OP_SUMSQ_MEAN;
+  GPMPC_CHECK_ARG((op >= GPMPC_GEMM_OP_NT && op <= GPMPC_GEMM_OP_ROWBLOCK) || sumsq);
+  // what gpmpc_gemm_diag refuses of the arguments the plan reads
+  GPMPC_CHECK_ARG(!(flags & GPMPC_GEMM_TRI_B) && (batch == 1 || (op != GPMPC_GEMM_OP_NN && op != GPMPC_GEMM_OP_TN)));
+  GPMPC_CHECK_ARG(!sumsq || (batch == 1 && !(flags & 7) && p0 >= -1 && p0 <= GEMM_SUMSQ_SPLITK && p1 >= 0));
+  GemmPolicy pol = gemm_policy_env();
+  if (policy) memcpy(&pol, policy, sizeof(pol));
+  GemmRequest r{op, M, N, K, batch, beta == 1.0, flags & 1, (flags >> 1) & 1};
+  r.no_scratch = (flags & GPMPC_GEMM_NO_SCRATCH) != 0;
+  if (op == GPMPC_GEMM_OP_ROWBLOCK) r.ksplit = p0;
+  if (sumsq) {  // launch_gemm_sumsq(_mean): a triangular [W; alpha^T] of n + n_out rows, one product
+    if (op == GPMPC_GEMM_OP_SUMSQ_MEAN) r.M += p1;
+    r.tri_a = 1, r.kind = p0;
+  }
+  const GemmPlan p = gemm_plan(pol, r);
+  memcpy(plan, &p, GPMPC_GEMM_PLAN_INTS * sizeof(int));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -165,6 +165,23 @@ int gpmpc_gemm_diag(gpmpc_ctx *ctx, int op, int M, int N, int K, int batch, cons
  * the launcher picks for it (0 64-row tiles, 1 128-row tiles, 2 the K split, 64-row tiles),
  * both under this process's GPMPC_GEMM128 / GPMPC_GEMM128_KMIN / GPMPC_SPLITK. */
 int gpmpc_gemm_row_tiles(int M, int N, int K, int *kind);
+/* diagnostic (tests only): what the launcher of op would do for the product, without
+ * touching a device (no context) -- the plan the launchers execute (csrc/gemm_plan.h).  op,
+ * flags, p0, p1 as for gpmpc_gemm_diag; only the ops with a decision: NT, NN, NN_BATCHED,
+ * TN, ROWBLOCK, SUMSQ, SUMSQ_MEAN (any other, or arguments gpmpc_gemm_diag refuses: -2).
+ * flags may add GPMPC_GEMM_NO_SCRATCH: the plan a launcher falls back to when the split-K
+ * partial buffer is not to be had.
+ * policy: NULL = this process's switches; else GPMPC_GEMM_POLICY_N ints in the order big,
+ * kmin, splitk, syrk128, streamk, ksplit, remap, xcd_batch, rowblock_xcd, post_xcd
+ * (GemmPolicy: the GPMPC_* switch of each and its default).  plan receives
+ * GPMPC_GEMM_PLAN_INTS ints: the path, split and grid gpmpc_gemm_diag reports (path -1: an
+ * empty product), the launch grid gx, gy, gz (of the split forms: of the partial products),
+ * the tile height (64 or 128) and the chunk length of the skinny K splits (else 0). */
+enum { GPMPC_GEMM_NO_SCRATCH = 8 };
+#define GPMPC_GEMM_POLICY_N 10
+#define GPMPC_GEMM_PLAN_INTS 8
+int gpmpc_gemm_plan(int op, int M, int N, int K, int batch, double beta, int flags, int p0, int p1,
+                    const int *policy, int *plan);
 /* diagnostic (tests only): the launches gpmpc_potrf_batched_dev would make for (n, batch),
  * without touching a device (no context).
  * policy: NULL = this process's switches; else GPMPC_POTRF_POLICY_N ints in the order p128,

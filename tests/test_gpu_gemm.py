@@ -23,6 +23,7 @@ import gemm_check as gc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 S = gc.SCALARS
+PLANNED = ("nt", "nn", "nn_batched", "tn", "rowblock", "sumsq", "sumsq_mean")   # the launchers with a decision
 
 
 def ab(i):
@@ -51,6 +52,10 @@ def run_case(ctx, case, path=None, split=None, grid=None, report=None):
     for name, want, have in (("path", path, got[0]), ("split", split, got[1]), ("grid", grid, got[2])):
         if want is not None and want != have:
             bad.append(f"{case.tag}: {name} {have!r}, meant for {want!r}")
+    if case.op in PLANNED:   # what ran is what the plan says, under this process's switches
+        plan = _lib.gemm_plan(case.op, case.M, case.N, case.K, case.batch, case.beta, case.flags, case.p0, case.p1)
+        if plan[:3] != got:
+            bad.append(f"{case.tag}: ran {got!r}, the plan is {plan!r}")
     if report is not None:
         for o in case.outs:
             if o.bound is not None:

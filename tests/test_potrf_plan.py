@@ -1,8 +1,7 @@
 """The batched Cholesky's launch plan, read without a GPU through gpmpc_potrf_plan (the same
 potrf_plan that launch_potrf_batched executes, csrc/potrf_plan.h): the regimes that
 test_gpu_parity.test_potrf_batched_dev and test_potrf_switch_paths say they cover, pinned;
-invariants of every plan over a sweep of shapes and switches; the switch names; and the
-one tile-height rule of the SUMSQ partial buffer (gemm_row_tiles = the launcher's pick).
+invariants of every plan over a sweep of shapes and switches; and the switch names.
 
 A step is (kind, c, K0, a0, a1, a2, a3) -- include/gpmpc.h lists the operands per kind."""
 import json
@@ -306,30 +305,3 @@ def test_one_switch_reader():
     src = open(os.path.join(CSRC, "potrf_plan.h")).read()
     assert not re.search(r"hipLaunch|hipError_t|hipStream_t|<hip/|<<<", src)
     assert re.findall(r'#include ["<]([^">]+)[">]', src) == ["climits", "../../include/gpmpc.h"]
-
-
-# ---- 4. one tile-height rule for the SUMSQ partial buffer ----------------------------------------
-
-_TILES_CHILD = r"""
-import json, os, sys
-sys.path.insert(0, os.getcwd())
-from gp_mpc_rocket_landing_amd import _lib as L
-g = [255, 256, 257, 300, 511, 512, 513]
-print(json.dumps([[M, N, K, *L.gemm_row_tiles(M, N, K)] for M in g for N in [20, 64] + g for K in g]))
-"""
-
-
-@pytest.mark.parametrize("env,kmin,big", [({}, 256, True), ({"GPMPC_GEMM128_KMIN": "512"}, 512, True),
-                                          ({"GPMPC_GEMM128": "0"}, 256, False)])
-def test_gemm_row_tiles_is_the_launchers_tile_height(env, kmin, big):
-    """The partial buffer's rows as its consumers count them (gemm_row_tiles) against the
-    kernel the launcher picks (gemm_sumsq_kind): 128-row tiles exactly when GPMPC_GEMM128 is on
-    and M, N >= 256, K >= GPMPC_GEMM128_KMIN (launch_gemm_impl's rule), 64-row tiles otherwise --
-    also under GPMPC_GEMM128_KMIN = 512 with 256 <= K < 512, where the two used to differ."""
-    rows = _child(_TILES_CHILD, env)
-    assert len(rows) == 7 * 9 * 7
-    for M, N, K, tiles, kind in rows:
-        want128 = big and M >= 256 and N >= 256 and K >= kmin
-        assert (kind == 1) == want128, (M, N, K, kind)
-        assert kind in (0, 1, 2) and (kind != 2 or (N <= 64 and K >= 256))
-        assert tiles == ((M + 127) // 128 if kind == 1 else (M + 63) // 64), (M, N, K, tiles, kind)
