@@ -166,6 +166,8 @@ _sig("gpmpc_gemm_diag", _c, _vp, _c, _c, _c, _c, _c, _vp, _i64, _i64, _vp, _i64,
      ctypes.c_double, ctypes.c_double, _c, _c, _c, _ip)
 _sig("gpmpc_gemm_row_tiles", _c, _c, _c, _c, _ip)
 _sig("gpmpc_potrf_plan", _c, _c, _c, _ip, _ip, _ip, _c)
+_sig("gpmpc_potrf_diag", _c, _vp, _c, _c, _vp, _c, _i64, _vp, _ip)
+_sig("gpmpc_tri_diag", _c, _vp, _c, _c, _c, _vp, _i64, _vp, _i64, _vp, _c)
 _sig("gpmpc_gemm_plan", _c, _c, _c, _c, _c, _c, ctypes.c_double, _c, _c, _c, _ip, _ip)
 _sig("gpmpc_gram_path", _c, _c, _c, _c)
 _sig("gpmpc_fleet_mc_attach", _c, _vp, ctypes.POINTER(FleetMCConfig), _dp)
@@ -213,7 +215,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_comm_count", "gpmpc_gather_results", "gpmpc_gather_prepare", "gpmpc_gather_collective", "gpmpc_rollout6_step_phases", "gpmpc_vfe_fit",
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
-            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan"]
+            "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
+            "gpmpc_tri_diag"]
 
 
 class HIPError(RuntimeError):
@@ -953,3 +956,66 @@ def potrf_plan(n, batch, **switches):
     if cnt < 0 or cnt > cap:
         _err(cnt, "potrf_plan")
     return POTRF_FORM[form.value], [(POTRF_STEP[r[0]], *map(int, r[1:])) for r in buf[:cnt]]
+
+
+def _potrf_policy(switches):
+    unknown = set(switches) - set(POTRF_POLICY)
+    if unknown:
+        raise TypeError(f"unknown potrf switches {sorted(unknown)}")
+    return np.array(list(dict(POTRF_POLICY, **switches).values()), np.int32)
+
+
+# ---- diagnostics: the batched Cholesky under an explicit policy, the triangular launchers ----
+def potrf_diag(ctx, A, n, batch, offset, ld, stride, info, **switches):
+    """gpmpc_potrf_batched_dev under an explicit policy (gpmpc_potrf_diag; tests only) on
+    ``batch`` matrices of order n inside the flat float64 device tensor A: the first at
+    element ``offset``, leading dimension ``ld``, ``stride`` elements apart.  info: an int32
+    device tensor of batch elements.  Without keywords the policy is this process's; with
+    any, the default policy with those fields of POTRF_POLICY replaced (as potrf_plan).
+    Raises ValueError before anything is launched when the description reaches past A."""
+    pol = _potrf_policy(switches)
+    n, batch, offset, ld, stride = int(n), int(batch), int(offset), int(ld), int(stride)
+    if A.dim() != 1 or A.dtype.itemsize != 8 or not A.is_contiguous() or not A.is_cuda:
+        raise ValueError("potrf_diag: A must be a flat contiguous float64 device tensor")
+    if n < 0 or batch < 0 or offset < 0 or ld < n or (batch > 1 and stride < (n - 1) * ld + n):
+        raise ValueError("potrf_diag: negative size, ld < n, or overlapping batch members")
+    if n and batch and offset + (batch - 1) * stride + (n - 1) * ld + n > A.numel():
+        raise ValueError("potrf_diag: the matrices reach past the tensor")
+    if info.numel() < batch or info.dtype.itemsize != 4 or not info.is_cuda:
+        raise ValueError("potrf_diag: info must be an int32 device tensor of batch elements")
+    _chk(_L.gpmpc_potrf_diag(ctx.h, n, batch, A.data_ptr() + 8 * offset, ld, stride, info.data_ptr(),
+                             _i(pol) if switches else None), "potrf_diag")
+
+
+TRI_OP = {"trsm": 0, "tri_inverse": 1, "cho_solve_inv": 2, "potrs_cols": 3}
+TRI_TRANS, TRI_RHS_LOWER = 1, 2
+
+
+def tri_diag(ctx, op, n, nrhs, L, X, W=None, flags=0):
+    """One triangular launcher or solve helper on device tensors (gpmpc_tri_diag; tests
+    only).  L, X, W are (flat float64 device tensor, offset, ld) triples: L n x n, X n x nrhs
+    (overwritten), W n x n (cho_solve_inv only).  Raises ValueError before anything is
+    launched when a description reaches past its tensor; HIPError (rc -2) when the arguments
+    are outside the launcher's contract."""
+    opc = TRI_OP[op] if isinstance(op, str) else int(op)
+    n, nrhs = int(n), int(nrhs)
+    if n < 1 or nrhs < 1:
+        raise ValueError("tri_diag: n and nrhs must be positive")
+
+    def ptr(name, d, rows, cols):
+        t, off, ld = d
+        off, ld = int(off), int(ld)
+        if t.dim() != 1 or t.dtype.itemsize != 8 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"tri_diag: operand {name} needs a flat contiguous float64 device tensor")
+        if off < 0 or ld < cols or off + (rows - 1) * ld + cols > t.numel():
+            raise ValueError(f"tri_diag: operand {name} has ld {ld} < {cols} or reaches past its tensor")
+        return t.data_ptr() + 8 * off, ld
+
+    pl, ldl = ptr("L", L, n, n)
+    px, ldx = ptr("X", X, n, nrhs)
+    pw = None
+    if W is not None:
+        pw, ldw = ptr("W", W, n, n)
+        if ldw != n:
+            raise ValueError("tri_diag: W is packed (ld n)")
+    _chk(_L.gpmpc_tri_diag(ctx.h, opc, n, nrhs, pl, ldl, px, ldx, pw, int(flags)), "tri_diag")

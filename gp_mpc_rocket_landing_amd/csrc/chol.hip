@@ -1236,8 +1236,8 @@ __global__ __launch_bounds__(256) void k_potrf_persist(int n, double *A, int64_t
 //   A[t0:n, t0:n] -= A[t0:n, K0:t0] A[t0:n, K0:t0]^T             (MFMA GEMM, K = 128)
 // so the O(n^3) work runs as K = 128 GEMMs on v_mfma_f64_16x16x4.
 #define OB 128
-hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int64_t lda,
-                                int64_t stride, int *info, double *Linv_scratch) {
+static hipError_t launch_potrf_batched32(hipStream_t s, int n, int batch, double *A, int64_t lda,
+                                         int64_t stride, int *info, double *Linv_scratch) {
   hipError_t e = hipMemsetAsync(info, 0, sizeof(int) * batch, s);
   if (e != hipSuccess) return e;
   auto at = [&](int r, int c) { return A + (int64_t)r * lda + c; };
@@ -1361,9 +1361,9 @@ static hipError_t launch_potrf_batched128(hipStream_t s, int n, int batch, doubl
   return hipGetLastError();
 }
 
+// under an explicit policy (gpmpc_potrf_diag); the product's entry below passes the process's
 hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int64_t lda,
-                                int64_t stride, int *info) {
-  const PotrfPolicy pol = potrf_policy_env();
+                                int64_t stride, int *info, const PotrfPolicy &pol) {
   const int form = potrf_form(pol);
   if (form == POTRF_FORM_PERSIST) {
     static bool attr = hipFuncSetAttribute((const void *)k_potrf_persist,
@@ -1385,7 +1385,12 @@ hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int6
   }
   double *Linv = (double *)gpmpc_scratch(s, 1, sizeof(double) * NB * NB * (size_t)batch);
   if (!Linv) return hipErrorOutOfMemory;
-  return launch_potrf_batched(s, n, batch, A, lda, stride, info, Linv);
+  return launch_potrf_batched32(s, n, batch, A, lda, stride, info, Linv);
+}
+
+hipError_t launch_potrf_batched(hipStream_t s, int n, int batch, double *A, int64_t lda,
+                                int64_t stride, int *info) {
+  return launch_potrf_batched(s, n, batch, A, lda, stride, info, potrf_policy_env());
 }
 
 // ---------------------------------------------------------------------------
@@ -1669,11 +1674,17 @@ extern "C" int gpmpc_potrf_batched_dev(gpmpc_ctx *ctx, int n, int batch, double 
 // diagnostic: the plan launch_potrf_batched would execute, no device touched
 static_assert(sizeof(PotrfPolicy) == GPMPC_POTRF_POLICY_N * sizeof(int) &&
               sizeof(PotrfStep) == GPMPC_POTRF_STEP_INTS * sizeof(int), "gpmpc_potrf_plan's layouts");
+// the policy argument of the two diagnostics (NULL: this process's); false: refused
+static bool potrf_policy_arg(const int *policy, PotrfPolicy &pol) {
+  pol = potrf_policy_env();
+  if (policy) memcpy(&pol, policy, sizeof(pol));
+  return pol.ob >= 0 && pol.ob <= 8 * DB && pol.ob % DB == 0;
+}
+
 extern "C" int gpmpc_potrf_plan(int n, int batch, const int *policy, int *form, int *steps, int cap) {
   GPMPC_CHECK_ARG(n >= 0 && batch >= 0 && form && cap >= 0 && (steps || cap == 0));
-  PotrfPolicy pol = potrf_policy_env();
-  if (policy) memcpy(&pol, policy, sizeof(pol));
-  GPMPC_CHECK_ARG(pol.ob >= 0 && pol.ob <= 8 * DB && pol.ob % DB == 0);
+  PotrfPolicy pol;
+  GPMPC_CHECK_ARG(potrf_policy_arg(policy, pol));
   *form = potrf_form(pol);
   int count = 0;
   if (*form == POTRF_FORM_128 && batch > 0)
@@ -1682,6 +1693,20 @@ extern "C" int gpmpc_potrf_plan(int n, int batch, const int *policy, int *form, 
       ++count;
     });
   return count;
+}
+
+// diagnostic (tests only): gpmpc_potrf_batched_dev under an explicit policy, so that every
+// form and switch runs inside one process
+extern "C" int gpmpc_potrf_diag(gpmpc_ctx *ctx, int n, int batch, double *dA, int lda, int64_t stride,
+                                int *dinfo, const int *policy) {
+  GPMPC_CHECK_ARG(ctx && dA && dinfo && n >= 0 && batch >= 0 && lda >= n);
+  GPMPC_CHECK_ARG(batch <= 1 || stride >= (int64_t)(n - 1) * lda + n);
+  PotrfPolicy pol;
+  GPMPC_CHECK_ARG(potrf_policy_arg(policy, pol));
+  if (n == 0 || batch == 0) return 0;
+  GPMPC_HIP(hipSetDevice(ctx->device));
+  GPMPC_HIP(launch_potrf_batched(ctx->stream, n, batch, dA, lda, stride, dinfo, pol));
+  return 0;
 }
 
 static int trsm_host(gpmpc_ctx *ctx, int n, int nrhs, const double *L, int ldl, double *B, int ldb,

@@ -520,6 +520,42 @@ static bool potrs_cols_ok(int n) {
   return env && attr && n <= POTRS_COLS_MAXN;
 }
 
+// diagnostic (tests only): one triangular launcher or solve helper on device pointers
+extern "C" int gpmpc_tri_diag(gpmpc_ctx *ctx, int op, int n, int nrhs, const double *dL, int64_t ldl, double *dX,
+                              int64_t ldx, const double *dW, int flags) {
+  GPMPC_CHECK_ARG(ctx && dL && dX && n >= 1 && nrhs >= 1 && ldl >= n);
+  GPMPC_CHECK_ARG(op >= GPMPC_TRI_OP_TRSM && op <= GPMPC_TRI_OP_POTRS_COLS);
+  const int trans = flags & GPMPC_TRI_TRANS, rhs_lower = flags & GPMPC_TRI_RHS_LOWER;
+  GPMPC_CHECK_ARG(!(flags & ~(GPMPC_TRI_TRANS | GPMPC_TRI_RHS_LOWER)) && (op == GPMPC_TRI_OP_TRSM || !flags));
+  GPMPC_CHECK_ARG(!(trans && rhs_lower));  // the backward walk has no triangular start
+  if (op == GPMPC_TRI_OP_TRSM) GPMPC_CHECK_ARG(ldx >= nrhs);
+  if (op == GPMPC_TRI_OP_TRI_INVERSE) GPMPC_CHECK_ARG(nrhs == n && ldx >= n);
+  // the solve helpers take their operands as the fits hold them: L and W at ld n, Y packed
+  if (op == GPMPC_TRI_OP_CHO_SOLVE_INV) GPMPC_CHECK_ARG(dW && nrhs <= 16 && ldl == n && ldx == nrhs);
+  if (op == GPMPC_TRI_OP_POTRS_COLS) GPMPC_CHECK_ARG(ldx == nrhs && potrs_cols_ok(n));
+  GPMPC_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  switch (op) {
+    case GPMPC_TRI_OP_TRSM:
+      GPMPC_HIP(launch_trsm_lower_ex(s, n, nrhs, dL, ldl, dX, ldx, trans ? 1 : 0, rhs_lower ? 1 : 0, nullptr));
+      break;
+    case GPMPC_TRI_OP_TRI_INVERSE: {
+      DevBuf tmp;
+      GPMPC_HIP(tmp.alloc(s, sizeof(double) * (size_t)n * n));
+      GPMPC_HIP(launch_tri_inverse(s, n, dL, ldl, dX, ldx, tmp.as<double>()));
+      break;
+    }
+    case GPMPC_TRI_OP_CHO_SOLVE_INV:
+      GPMPC_HIP(cho_solve_inv(s, n, nrhs, dL, dW, dX));
+      break;
+    case GPMPC_TRI_OP_POTRS_COLS:
+      hipLaunchKernelGGL(k_potrs_cols, dim3(nrhs), dim3(256), sizeof(double) * n, s, n, dL, ldl, dX, nrhs);
+      GPMPC_HIP(hipGetLastError());
+      break;
+  }
+  return 0;
+}
+
 static int exact_fit(gpmpc_ctx *ctx, int kind, const double *X, int n, int d, const double *Y, int n_out,
                      const double *ls, double sigma2, double noise, const KProgArg *prog, gpmpc_gp **out,
                      double *y_mean, double *y_std, double *lml, int *jitter_steps) {

@@ -204,6 +204,26 @@ enum { GPMPC_POTRF_DIAG = 0, GPMPC_POTRF_UPD_SYRK_DIAG = 1, GPMPC_POTRF_UPD_ROWB
        GPMPC_POTRF_PSOLVE_TRSM = 4, GPMPC_POTRF_PSOLVE_LAT = 5, GPMPC_POTRF_PSOLVE_ROWBLOCK = 6,
        GPMPC_POTRF_TRAIL_LAT = 7, GPMPC_POTRF_TRAIL_SYRK = 8 };
 int gpmpc_potrf_plan(int n, int batch, const int *policy, int *form, int *steps, int cap);
+/* diagnostic (tests only): gpmpc_potrf_batched_dev under an explicit policy (as for
+ * gpmpc_potrf_plan: NULL = this process's switches), so that every form and switch runs in
+ * one process.  A policy gpmpc_potrf_plan refuses, or batch > 1 members that overlap
+ * (stride < (n - 1) lda + n), returns -2 and launches nothing. */
+int gpmpc_potrf_diag(gpmpc_ctx *ctx, int n, int batch, double *dA, int lda, int64_t stride, int *dinfo,
+                     const int *policy);
+/* diagnostic (tests only): one triangular launcher or solve helper on device pointers (row-
+ * major, L n x n lower at ld ldl, X n x nrhs at ld ldx, overwritten):
+ *   TRSM           X <- L^-1 X, or L^-T X under GPMPC_TRI_TRANS; GPMPC_TRI_RHS_LOWER (forward
+ *                  only): X is lower triangular (zero above its diagonal), which the walk uses
+ *   TRI_INVERSE    X <- L^-1 by the doubling inverse; X preset to the identity, nrhs = n
+ *   CHO_SOLVE_INV  X <- (L L^T)^-1 X through W = L^-1 (dW, ld n) with one refinement step;
+ *                  nrhs <= 16, ldl = n, ldx = nrhs
+ *   POTRS_COLS     X <- (L L^T)^-1 X by the per-column substitution kernel; ldx = nrhs
+ * Arguments outside a launcher's contract return -2 and launch nothing. */
+enum { GPMPC_TRI_OP_TRSM = 0, GPMPC_TRI_OP_TRI_INVERSE = 1, GPMPC_TRI_OP_CHO_SOLVE_INV = 2,
+       GPMPC_TRI_OP_POTRS_COLS = 3 };
+enum { GPMPC_TRI_TRANS = 1, GPMPC_TRI_RHS_LOWER = 2 };
+int gpmpc_tri_diag(gpmpc_ctx *ctx, int op, int n, int nrhs, const double *dL, int64_t ldl, double *dX, int64_t ldx,
+                   const double *dW, int flags);
 
 /* ---- a4-a6: exact GP ------------------------------------------------------
  * MultiOutputExactGP.fit (exact_gp.py:476-499 -> ExactGP.fit :118-184) for
