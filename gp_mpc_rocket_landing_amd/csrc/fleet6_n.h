@@ -267,54 +267,6 @@ __device__ __forceinline__ int r6_tid() {
 
 __device__ __forceinline__ int r6_tri(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
 
-template <int K>
-__device__ __forceinline__ void r6_max(double (&v)[K], double (*red)[12]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = fmax(v[k], __shfl_xor(v[k], o));
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double m = red[0][k];
-    for (int w = 1; w < R6_T / 64; ++w) m = fmax(m, red[w][k]);
-    v[k] = m;
-  }
-  __syncthreads();
-}
-
-template <int K>
-__device__ __forceinline__ void r6_sum(double (&v)[K], double (*red)[12]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = red[0][k];
-    for (int w = 1; w < R6_T / 64; ++w) s += red[w][k];
-    v[k] = s;
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ double r6_rho(double l, double u, double rs) {
-  if (l < -QP_OSQP_INFTY * QP_MIN_SCALING && u > QP_OSQP_INFTY * QP_MIN_SCALING) return QP_RHO_MIN;
-  if (u - l < QP_RHO_TOL) return QP_RHO_EQ * rs;
-  return rs;
-}
-
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -549,7 +501,7 @@ __device__ __forceinline__ int r6_factor(R6Smem &s, R6Var (&V)[2], R6Row (&R)[2]
       for (int e = 0; e < R6_SZ; ++e) s.G[(R[h].k * R6_NX + R[h].i) * R6_SZ + e] = R[h].A[e];
     if (V[h].ok) {
       s.dsc[V[h].j] = V[h].P + sigma;
-      s.xs[V[h].j] = r6_rho(V[h].lb, V[h].ub, rs) * V[h].Ab * V[h].Ab;
+      s.xs[V[h].j] = qp_row_rho(V[h].lb, V[h].ub, rs) * V[h].Ab * V[h].Ab;
     }
   }
   __syncthreads();
@@ -821,7 +773,7 @@ _Pragma(R6_STR(unroll R6_CHAIN_UNROLL))
   mark(6);
 }
 
-// residual norms (auxil.c update_info) + the rho-estimate quantities (as fq_update_info)
+// residual norms (auxil.c update_info) + the rho-estimate quantities (qp_rules.h qp_acc_*)
 __device__ __forceinline__ void r6_update_info(R6Smem &s, R6Var (&V)[2], R6Row (&R)[2], double (&o)[8],
                                                double (&re_)[4]) {
   R6_FOR_H {
@@ -831,42 +783,23 @@ __device__ __forceinline__ void r6_update_info(R6Smem &s, R6Var (&V)[2], R6Row (
   }
   __syncthreads();
   double v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto row = [&](double ax, double z, double e) {
-    v[0] = fmax(v[0], fabs((ax - z) / e));
-    v[1] = fmax(v[1], fabs(z / e));
-    v[2] = fmax(v[2], fabs(ax / e));
-    v[8] = fmax(v[8], fabs(ax - z));
-    v[9] = fmax(v[9], fmax(fabs(z), fabs(ax)));
-  };
+  // (a lambda, not the rule called directly: called directly, the compiler lays the whole
+  // control kernel out differently -- other register counts and scratch in some horizons)
+  auto row = [&](double ax, double z, double e) { qp_acc_row(v, ax, z, e); };
   R6_FOR_H {
     R6Var &W = V[h];
     if (R[h].ok) row(r6_row_dot(R[h], s.rhs), R[h].zr, s.E[R[h].r]);
     if (W.ok) {
       row(0.0 + W.Ab * W.x, W.zb, s.E[R6_MD + W.j]);
-      const double aty = r6_col_dot(s, W, s.w, W.yb, s.w + R6_MD);
-      const double px = W.P * W.x, d = W.D, q = W.q;
-      v[3] = fmax(v[3], fabs((q + px + aty) / d));
-      v[4] = fmax(v[4], fabs(q / d));
-      v[5] = fmax(v[5], fabs(aty / d));
-      v[6] = fmax(v[6], fabs(px / d));
-      v[10] = fmax(v[10], fabs(q + px + aty));
-      v[11] = fmax(v[11], fmax(fmax(fabs(q), fabs(aty)), fabs(px)));
+      qp_acc_var(v, W.q, W.P * W.x, r6_col_dot(s, W, s.w, W.yb, s.w + R6_MD), W.D);
     }
     if (W.gok) row(r6_gen_dot(W, s.rhs), W.gz, s.E[R6_MD + R6_NV + W.j]);
   }
-  r6_max<12>(v, s.red);
+  wg_max<12, R6_T / 64>(v, s.red);
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = v[k];
 #pragma unroll
   for (int k = 0; k < 4; ++k) re_[k] = v[8 + k];
-}
-
-__device__ __forceinline__ double r6_proj(double d, double l, double u) {
-  const bool bu = u > QP_OSQP_INFTY * QP_MIN_SCALING, bl = l < -QP_OSQP_INFTY * QP_MIN_SCALING;
-  if (bu && bl) return 0.0;
-  if (bu) return fmin(d, 0.0);
-  if (bl) return fmax(d, 0.0);
-  return d;
 }
 
 __device__ __forceinline__ bool r6_primal_infeasible(R6Smem &s, R6Var (&V)[2], R6Row (&R)[2], R6Dy (&Dl)[2],
@@ -876,11 +809,11 @@ __device__ __forceinline__ bool r6_primal_infeasible(R6Smem &s, R6Var (&V)[2], R
     R6Var &W = V[h];
     R6Row &Q = R[h];
     R6Dy &d = Dl[h];
-    if (Q.ok) { d.dyb = r6_proj(d.dyb, Q.ur, Q.ur); v[0] = fmax(v[0], fabs(s.E[Q.r] * d.dyb)); }
-    if (W.ok) { d.dyb = r6_proj(d.dyb, W.lb, W.ub); v[0] = fmax(v[0], fabs(s.E[R6_MD + W.j] * d.dyb)); }
-    if (W.gok) { d.gdy = r6_proj(d.gdy, W.gl, W.gu); v[0] = fmax(v[0], fabs(s.E[R6_MD + R6_NV + W.j] * d.gdy)); }
+    if (Q.ok) { d.dyb = qp_polar(d.dyb, Q.ur, Q.ur); v[0] = fmax(v[0], fabs(s.E[Q.r] * d.dyb)); }
+    if (W.ok) { d.dyb = qp_polar(d.dyb, W.lb, W.ub); v[0] = fmax(v[0], fabs(s.E[R6_MD + W.j] * d.dyb)); }
+    if (W.gok) { d.gdy = qp_polar(d.gdy, W.gl, W.gu); v[0] = fmax(v[0], fabs(s.E[R6_MD + R6_NV + W.j] * d.gdy)); }
   }
-  r6_max<1>(v, s.red);
+  wg_max<1, R6_T / 64>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double sm[1] = {0.0};
@@ -888,11 +821,11 @@ __device__ __forceinline__ bool r6_primal_infeasible(R6Smem &s, R6Var (&V)[2], R
     R6Var &W = V[h];
     R6Row &Q = R[h];
     const R6Dy &d = Dl[h];
-    if (Q.ok) sm[0] += Q.ur * fmax(d.dyb, 0.0) + Q.ur * fmin(d.dyb, 0.0);
-    if (W.ok) sm[0] += W.ub * fmax(d.dyb, 0.0) + W.lb * fmin(d.dyb, 0.0);
-    if (W.gok) sm[0] += W.gu * fmax(d.gdy, 0.0) + W.gl * fmin(d.gdy, 0.0);
+    if (Q.ok) sm[0] += qp_support(d.dyb, Q.ur, Q.ur);
+    if (W.ok) sm[0] += qp_support(d.dyb, W.lb, W.ub);
+    if (W.gok) sm[0] += qp_support(d.gdy, W.gl, W.gu);
   }
-  r6_sum<1>(sm, s.red);
+  wg_sum<1, R6_T / 64>(sm, s.red);
   if (!(sm[0] < -eps * nrm)) return false;
   R6_FOR_H {
     if (R[h].ok) s.w[R[h].r] = Dl[h].dyb;
@@ -903,7 +836,7 @@ __device__ __forceinline__ bool r6_primal_infeasible(R6Smem &s, R6Var (&V)[2], R
   R6_FOR_H {
     if (V[h].ok) mx[0] = fmax(mx[0], fabs(r6_col_dot(s, V[h], s.w, Dl[h].dyb, s.w + R6_MD) / V[h].D));
   }
-  r6_max<1>(mx, s.red);
+  wg_max<1, R6_T / 64>(mx, s.red);
   return mx[0] < eps * nrm;
 }
 
@@ -913,15 +846,15 @@ __device__ __forceinline__ bool r6_dual_infeasible(R6Smem &s, R6Var (&V)[2], R6R
   R6_FOR_H {
     if (V[h].ok) v[0] = fmax(v[0], fabs(V[h].D * Dl[h].dx));
   }
-  r6_max<1>(v, s.red);
+  wg_max<1, R6_T / 64>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double a[1] = {0.0}, pm[1] = {0.0};
   R6_FOR_H {
     if (V[h].ok) { a[0] += V[h].q * Dl[h].dx; pm[0] = fmax(pm[0], fabs(V[h].P * Dl[h].dx / V[h].D)); }
   }
-  r6_sum<1>(a, s.red);
-  r6_max<1>(pm, s.red);
+  wg_sum<1, R6_T / 64>(a, s.red);
+  wg_max<1, R6_T / 64>(pm, s.red);
   if (!(a[0] < s.c * eps * nrm)) return false;
   if (!(pm[0] < s.c * eps * nrm)) return false;
   R6_FOR_H {
@@ -930,9 +863,7 @@ __device__ __forceinline__ bool r6_dual_infeasible(R6Smem &s, R6Var (&V)[2], R6R
   __syncthreads();
   double bad[1] = {0.0};
   auto test = [&](double vv, double l, double u) {
-    if ((u < QP_OSQP_INFTY * QP_MIN_SCALING && vv > eps * nrm) ||
-        (l > -QP_OSQP_INFTY * QP_MIN_SCALING && vv < -eps * nrm))
-      bad[0] = 1.0;
+    if (qp_recedes_bad(vv, l, u, eps * nrm)) bad[0] = 1.0;
   };
   R6_FOR_H {
     R6Var &W = V[h];
@@ -940,32 +871,15 @@ __device__ __forceinline__ bool r6_dual_infeasible(R6Smem &s, R6Var (&V)[2], R6R
     if (W.ok) test((0.0 + W.Ab * Dl[h].dx) / s.E[R6_MD + W.j], W.lb, W.ub);
     if (W.gok) test(r6_gen_dot(W, s.rhs) / s.E[R6_MD + R6_NV + W.j], W.gl, W.gu);
   }
-  r6_max<1>(bad, s.red);
+  wg_max<1, R6_T / 64>(bad, s.red);
   return bad[0] == 0.0;
-}
-
-__device__ __forceinline__ bool r6_check(R6Smem &s, R6Var (&V)[2], R6Row (&R)[2], R6Dy (&Dl)[2], const QPSettingsDev &st,
-                                         const double (&o)[8], bool approx, int &status) {
-  const double pri = o[0], dua = o[3] / s.c;
-  double ea = st.eps_abs, er = st.eps_rel, epi = st.eps_prim_inf, edi = st.eps_dual_inf;
-  if (pri > QP_OSQP_INFTY || dua > QP_OSQP_INFTY) { status = -7; return true; }
-  if (approx) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-  bool prim_ok = false, prim_inf = false, dual_ok = false, dual_inf = false;
-  if (pri < ea + er * fmax(o[1], o[2])) prim_ok = true;
-  else prim_inf = r6_primal_infeasible(s, V, R, Dl, epi);
-  if (dua < ea + er * fmax(fmax(o[4], o[5]), o[6]) / s.c) dual_ok = true;
-  else dual_inf = r6_dual_infeasible(s, V, R, Dl, edi);
-  if (prim_ok && dual_ok) { status = approx ? 2 : 1; return true; }
-  if (prim_inf) { status = approx ? 3 : -3; return true; }
-  if (dual_inf) { status = approx ? 4 : -4; return true; }
-  return false;
 }
 
 __device__ __forceinline__ void r6_rebuild_w(R6Smem &s, R6Var (&V)[2], R6Row (&R)[2]) {
   const double rs = s.rho_s;
   R6_FOR_H {
     if (R[h].ok) s.w[R[h].r] = QP_RHO_EQ * rs * R[h].zr - R[h].yr;
-    if (V[h].gok) s.w[R6_MD + V[h].j] = r6_rho(V[h].gl, V[h].gu, rs) * V[h].gz - V[h].gy;
+    if (V[h].gok) s.w[R6_MD + V[h].j] = qp_row_rho(V[h].gl, V[h].gu, rs) * V[h].gz - V[h].gy;
   }
   __syncthreads();
 }
@@ -1102,7 +1016,7 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
       }
       Q.yr = ysc[Q.r];
     }
-    // ---- OSQP solve (qp_device.h order): clip bounds, Ruiz scaling, rho, factor
+    // ---- OSQP solve (the rules of qp_rules.h): clip bounds, Ruiz scaling, rho, factor
     if (W.ok) { W.lb = fmax(W.lb, -QP_OSQP_INFTY); W.ub = fmin(W.ub, QP_OSQP_INFTY); }
     if (W.gok) { W.gl = fmax(W.gl, -QP_OSQP_INFTY); W.gu = fmin(W.gu, QP_OSQP_INFTY); }
     if (Q.ok) Q.ur = fmin(fmax(Q.ur, -QP_OSQP_INFTY), QP_OSQP_INFTY);
@@ -1200,8 +1114,8 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
         mx[0] = fmax(mx[0], fabs(W.q));
       }
     }
-    r6_sum<1>(v, s.red);
-    r6_max<1>(mx, s.red);
+    wg_sum<1, R6_T / 64>(v, s.red);
+    wg_max<1, R6_T / 64>(mx, s.red);
     double ct = v[0] / R6_NV;
     const double nq = qp_limit(mx[0]);
     ct = qp_limit(fmax(ct, nq));
@@ -1238,7 +1152,7 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
         const double rs = s.rho_s;
         R6_FOR_H {
           // the bound row's rho z - y (formed here rather than kept per item)
-          const double ztb = r6_rho(V[h].lb, V[h].ub, rs) * V[h].zb - V[h].yb;
+          const double ztb = qp_row_rho(V[h].lb, V[h].ub, rs) * V[h].zb - V[h].yb;
           if (V[h].ok) s.rhs[V[h].j] = sig * V[h].x - V[h].q + r6_col_dot(s, V[h], s.w, ztb, s.w + R6_MD);
         }
       }
@@ -1254,58 +1168,42 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
         R6Var &W = V[h];
         R6Row &Q = R[h];
         if (W.ok) {
-          const double xt = s.xs[W.j], xo = W.x;
-          const double xn = al * xt + (1.0 - al) * xo;
-          Dl[h].dx = xn - xo;
-          W.x = xn;
-          const double ztl = 0.0 + W.Ab * xt;
-          const double rho = r6_rho(W.lb, W.ub, rs), zo = W.zb, yo = W.yb;
-          const double zr = al * ztl + (1.0 - al) * zo;
-          double zn = zr + yo / rho;
-          zn = fmin(fmax(zn, W.lb), W.ub);
-          const double d = rho * (zr - zn);
-          Dl[h].dyb = d; W.yb = yo + d; W.zb = zn;
+          const double xt = s.xs[W.j];
+          const QPXStep xs = qp_x_step(al, xt, W.x);
+          Dl[h].dx = xs.dx;
+          W.x = xs.xn;
+          const QPRowStep d = qp_row_step(al, 0.0 + W.Ab * xt, qp_row_rho(W.lb, W.ub, rs), W.lb, W.ub, W.zb, W.yb);
+          Dl[h].dyb = d.dy; W.yb = d.yn; W.zb = d.zn;
         }
         if (W.gok) {
-          const double ztl = r6_gen_dot(W, s.xs);
-          const double rho = r6_rho(W.gl, W.gu, rs), zo = W.gz, yo = W.gy;
-          const double zr = al * ztl + (1.0 - al) * zo;
-          double zn = zr + yo / rho;
-          zn = fmin(fmax(zn, W.gl), W.gu);
-          const double d = rho * (zr - zn);
-          Dl[h].gdy = d; W.gy = yo + d; W.gz = zn;
+          const QPRowStep d = qp_row_step(al, r6_gen_dot(W, s.xs), qp_row_rho(W.gl, W.gu, rs), W.gl, W.gu, W.gz, W.gy);
+          Dl[h].gdy = d.dy; W.gy = d.yn; W.gz = d.zn;
         }
         if (Q.ok) {
-          const double ztl = r6_row_dot(Q, s.xs);
-          const double rho = QP_RHO_EQ * rs, zo = Q.zr, yo = Q.yr;
-          const double zr = al * ztl + (1.0 - al) * zo;
-          double zn = zr + yo / rho;
-          zn = fmin(fmax(zn, Q.ur), Q.ur);
-          const double d = rho * (zr - zn);
-          Dl[h].dyb = d; Q.yr = yo + d; Q.zr = zn;
+          const QPRowStep d = qp_row_step(al, r6_row_dot(Q, s.xs), QP_RHO_EQ * rs, Q.ur, Q.ur, Q.zr, Q.yr);
+          Dl[h].dyb = d.dy; Q.yr = d.yn; Q.zr = d.zn;
         }
       }
       __syncthreads();  // every read of s.w / s.xs of this iteration is done
       R6_FOR_H {
         if (R[h].ok) s.w[R[h].r] = QP_RHO_EQ * rs * R[h].zr - R[h].yr;
-        if (V[h].gok) s.w[R6_MD + V[h].j] = r6_rho(V[h].gl, V[h].gu, rs) * V[h].gz - V[h].gy;
+        if (V[h].gok) s.w[R6_MD + V[h].j] = qp_row_rho(V[h].gl, V[h].gu, rs) * V[h].gz - V[h].gy;
       }
       __syncthreads();
       mark(7);
-      const bool can_check = st.check_termination && (it % st.check_termination == 0);
-      const bool adapt = st.adaptive_rho && st.adaptive_rho_interval && (it % st.adaptive_rho_interval == 0);
+      bool can_check, adapt;
+      qp_due(st, it, can_check, adapt);
       const bool last = it == st.max_iter;
+      auto prim_inf = [&](double eps) { return r6_primal_infeasible(s, V, R, Dl, eps); };
+      auto dual_inf = [&](double eps) { return r6_dual_infeasible(s, V, R, Dl, eps); };
       if (can_check || adapt || last) {
         res.iter = it;
         r6_update_info(s, V, R, o, re_);
       }
-      if (can_check && r6_check(s, V, R, Dl, st, o, false, res.status)) break;
+      if (can_check && qp_terminated(o, s.c, st, false, res.status, prim_inf, dual_inf)) break;
       if (adapt) {
-        const double pr = re_[0] / (re_[1] + 1e-10);
-        const double du = re_[2] / (re_[3] + 1e-10);
-        double est = s.rho_s * sqrt(pr / (du + 1e-10));
-        est = fmin(fmax(est, QP_RHO_MIN), QP_RHO_MAX);
-        if (est > s.rho_s * st.adaptive_rho_tolerance || est < s.rho_s / st.adaptive_rho_tolerance) {
+        const double est = qp_rho_estimate(re_, s.rho_s);
+        if (qp_rho_moved(est, s.rho_s, st.adaptive_rho_tolerance)) {
           __syncthreads();
           if (tid == 0) s.rho_s = est;
           __syncthreads();
@@ -1322,7 +1220,7 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
         // check unless one just ran, then the approximate one (qp_device.h).  max_iter
         // >= 1 always: r6_create refuses less, as OSQP's settings check does
         for (int ap = can_check ? 1 : 0; ap < 2; ++ap) {
-          if (r6_check(s, V, R, Dl, st, o, ap == 1, res.status)) break;
+          if (qp_terminated(o, s.c, st, ap == 1, res.status, prim_inf, dual_inf)) break;
           if (ap == 1) res.status = -2;
         }
       }
@@ -1364,7 +1262,7 @@ __global__ __launch_bounds__(R6_T) void k_r6_control(R6Args a) {
     // _solve_qp's fallback (gp_mpc.py:478-482): the nominal trajectory
     for (int e = tid; e < (R6_N + 1) * R6_NX; e += R6_T) Xo[e] = Xb[e];
   }
-  if (a.mode) r6_max<2>(chg, s.red);  // a.mode is uniform over the launch
+  if (a.mode) wg_max<2, R6_T / 64>(chg, s.red);  // a.mode is uniform over the launch
   if (tid == 0 && a.mode) {  // GPMPC.solve pass bookkeeping
     a.passes[b] += 1;
     a.qit[b] += res.iter;

@@ -405,7 +405,7 @@ __global__ __launch_bounds__(FQ_T) __attribute__((amdgpu_waves_per_eu(FQ_WPE, FQ
         const double old = (j >= Nv) ? Xw[N * NX + i] : (i < NX ? Xw[k * NX + i] : Uw[k * NU + i - NX]);
         dm[0] = fmax(dm[0], fabs(s.rhs[j] - old));
       }
-    fq_max<1>(dm, s.red);  // (its barriers order the reads of Xw / Uw before the writes)
+    wg_max<1, FQ_NW>(dm, s.red);  // (its barriers order the reads of Xw / Uw before the writes)
     for (int e = tid; e < (N + 1) * NX; e += FQ_T) {
       const int k = e / NX, i = e - k * NX;
       Xw[e] = s.rhs[(k == N) ? Nv + i : k * (NX + NU) + i];

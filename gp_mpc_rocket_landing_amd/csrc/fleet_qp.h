@@ -116,78 +116,6 @@ struct FleetSmem {
   __device__ double *band() { return band_store; }
 };
 
-template <int K>
-__device__ __forceinline__ void fq_max(double (&v)[K], double (*red)[16]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = fmax(v[k], __shfl_xor(v[k], o));
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double m = red[0][k];
-#pragma unroll
-    for (int w = 1; w < FQ_NW; ++w) m = fmax(m, red[w][k]);
-    v[k] = m;
-  }
-  __syncthreads();
-}
-
-template <int K>
-__device__ __forceinline__ void fq_sum(double (&v)[K], double (*red)[16]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double t = red[0][k];
-#pragma unroll
-    for (int w = 1; w < FQ_NW; ++w) t += red[w][k];
-    v[k] = t;
-  }
-  __syncthreads();
-}
-
-// block-wide sum of a and max of b in one exchange (3 barriers instead of 6);
-// each tree is fq_sum's / fq_max's
-__device__ __forceinline__ void fq_sum_max(double &a, double &b, double (*red)[16]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o);
-    b = fmax(b, __shfl_xor(b, o));
-  }
-  __syncthreads();
-  if (lane == 0) { red[wv][0] = a; red[wv][1] = b; }
-  __syncthreads();
-  a = red[0][0];
-  b = red[0][1];
-#pragma unroll
-  for (int w = 1; w < FQ_NW; ++w) {
-    a += red[w][0];
-    b = fmax(b, red[w][1]);
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ double fq_rho(double l, double u, double rs) {
-  if (l < -QP_OSQP_INFTY * QP_MIN_SCALING && u > QP_OSQP_INFTY * QP_MIN_SCALING) return QP_RHO_MIN;
-  if (u - l < QP_RHO_TOL) return QP_RHO_EQ * rs;
-  return rs;
-}
-
 // per-thread state: 2 variable slots (+ their bound rows), 2 dynamics-row slots
 struct FleetRegs {
   bool vok[2], rok[2];
@@ -397,7 +325,7 @@ __device__ __forceinline__ void fq_scale(const QPPattern &pt, FleetSmem &s, Flee
 #pragma unroll
     for (int h = 0; h < FQ_H; ++h)
       if (R.vok[h]) mx[0] = fmax(mx[0], fabs(R.q[h]));
-    fq_sum_max(v[0], mx[0], s.red);  // (its barriers also order the A / rhs updates above)
+    wg_sum_max<FQ_NW>(v[0], mx[0], s.red);  // (its barriers also order the A / rhs updates above)
     double ct = v[0] / n;
     const double nq = qp_limit(mx[0]);
     ct = qp_limit(fmax(ct, nq));
@@ -480,7 +408,7 @@ __device__ __forceinline__ int fq_factor(const QPPattern &pt, FleetSmem &s, Flee
     double v = R.P[h] + sigma;
 #pragma unroll
     for (int k = 0; k < FQ_CMAX; ++k) v += re * a[k] * a[k];
-    v += fq_rho(R.lb[h], R.ub[h], rs) * R.Ab[h] * R.Ab[h];
+    v += qp_row_rho(R.lb[h], R.ub[h], rs) * R.Ab[h] * R.Ab[h];
     s.band_store[e] = v;
   }
   if (tid == 0) s.zslot = 0.0;
@@ -510,9 +438,8 @@ __device__ __forceinline__ int fq_factor(const QPPattern &pt, FleetSmem &s, Flee
   return s.flag;
 }
 
-// residual norms (auxil.c update_info) and the rho-estimate quantities in one pass:
-// o: 0 pri  1 |z/E|  2 |Ax/E|  3 dua*c  4 |q/D|  5 |A'y/D|  6 |Px/D|
-// re: 0 |Ax - z|  1 max(|z|,|Ax|)  2 |q + Px + A'y|  3 max(|q|,|A'y|,|Px|)   (scaled)
+// residual norms (auxil.c update_info) and the rho-estimate quantities in one pass
+// (qp_rules.h qp_acc_*: o = v[0..7], re = v[8..11])
 __device__ __forceinline__ void fq_update_info(FleetSmem &s, FleetRegs &R, double (&o)[8], double (&re)[4]) {
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h) {
@@ -526,36 +453,17 @@ __device__ __forceinline__ void fq_update_info(FleetSmem &s, FleetRegs &R, doubl
     if (R.rok[h]) {  // dynamics row: (A x)_r
       double ax = 0.0;
       _Pragma("unroll") for (int e = 0; e < FQ_RMAX; ++e) ax += s.A[R.rb(h) + e] * s.rhs[R.rc(h, e)];
-      const double e = s.E[R.rr[h]], z = R.zr(h);
-      v[0] = fmax(v[0], fabs((ax - z) / e));
-      v[1] = fmax(v[1], fabs(z / e));
-      v[2] = fmax(v[2], fabs(ax / e));
-      v[8] = fmax(v[8], fabs(ax - z));
-      v[9] = fmax(v[9], fmax(fabs(z), fabs(ax)));
+      qp_acc_row(v, ax, R.zr(h), s.E[R.rr[h]]);
     }
     if (R.vok[h]) {
-      {  // bound row
-        const double ax = 0.0 + R.Ab[h] * R.x[h];
-        const double e = s.E[FQ_MD + R.vj[h]], z = R.zb_(h);
-        v[0] = fmax(v[0], fabs((ax - z) / e));
-        v[1] = fmax(v[1], fabs(z / e));
-        v[2] = fmax(v[2], fabs(ax / e));
-        v[8] = fmax(v[8], fabs(ax - z));
-        v[9] = fmax(v[9], fmax(fabs(z), fabs(ax)));
-      }
+      qp_acc_row(v, 0.0 + R.Ab[h] * R.x[h], R.zb_(h), s.E[FQ_MD + R.vj[h]]);  // bound row
       double aty = 0.0;  // (A' y)_j in CSC order, the bound row last
       _Pragma("unroll") for (int e = 0; e < FQ_CMAX; ++e) aty += s.A[R.ca(h, e)] * s.zt[R.cr(h, e)];
       aty += R.Ab[h] * R.yb_(h);
-      const double px = R.P[h] * R.x[h], d = R.D[h], q = R.q[h];
-      v[3] = fmax(v[3], fabs((q + px + aty) / d));
-      v[4] = fmax(v[4], fabs(q / d));
-      v[5] = fmax(v[5], fabs(aty / d));
-      v[6] = fmax(v[6], fabs(px / d));
-      v[10] = fmax(v[10], fabs(q + px + aty));
-      v[11] = fmax(v[11], fmax(fmax(fabs(q), fabs(aty)), fabs(px)));
+      qp_acc_var(v, R.q[h], R.P[h] * R.x[h], aty, R.D[h]);
     }
   }
-  fq_max<12>(v, s.red);
+  wg_max<12, FQ_NW>(v, s.red);
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = v[k];
 #pragma unroll
@@ -564,35 +472,27 @@ __device__ __forceinline__ void fq_update_info(FleetSmem &s, FleetRegs &R, doubl
 
 __device__ __forceinline__ bool fq_primal_infeasible(FleetSmem &s, FleetRegs &R, double eps) {
   double v[1] = {0.0};
-  auto proj = [](double d, double l, double u) {
-    const bool bu = u > QP_OSQP_INFTY * QP_MIN_SCALING;
-    const bool bl = l < -QP_OSQP_INFTY * QP_MIN_SCALING;
-    if (bu && bl) return 0.0;
-    if (bu) return fmin(d, 0.0);
-    if (bl) return fmax(d, 0.0);
-    return d;
-  };
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h) {
     if (R.rok[h]) {
-      R.dyr(h) = proj(R.dyr(h), R.ur(h), R.ur(h));
+      R.dyr(h) = qp_polar(R.dyr(h), R.ur(h), R.ur(h));
       v[0] = fmax(v[0], fabs(s.E[R.rr[h]] * R.dyr(h)));
     }
     if (R.vok[h]) {
-      R.dyb_(h) = proj(R.dyb_(h), R.lb[h], R.ub[h]);
+      R.dyb_(h) = qp_polar(R.dyb_(h), R.lb[h], R.ub[h]);
       v[0] = fmax(v[0], fabs(s.E[FQ_MD + R.vj[h]] * R.dyb_(h)));
     }
   }
-  fq_max<1>(v, s.red);
+  wg_max<1, FQ_NW>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double sm[1] = {0.0};
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h) {
-    if (R.rok[h]) sm[0] += R.ur(h) * fmax(R.dyr(h), 0.0) + R.ur(h) * fmin(R.dyr(h), 0.0);
-    if (R.vok[h]) sm[0] += R.ub[h] * fmax(R.dyb_(h), 0.0) + R.lb[h] * fmin(R.dyb_(h), 0.0);
+    if (R.rok[h]) sm[0] += qp_support(R.dyr(h), R.ur(h), R.ur(h));
+    if (R.vok[h]) sm[0] += qp_support(R.dyb_(h), R.lb[h], R.ub[h]);
   }
-  fq_sum<1>(sm, s.red);
+  wg_sum<1, FQ_NW>(sm, s.red);
   if (!(sm[0] < -eps * nrm)) return false;
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h)
@@ -607,7 +507,7 @@ __device__ __forceinline__ bool fq_primal_infeasible(FleetSmem &s, FleetRegs &R,
       acc += R.Ab[h] * R.dyb_(h);
       mx[0] = fmax(mx[0], fabs(acc / R.D[h]));
     }
-  fq_max<1>(mx, s.red);
+  wg_max<1, FQ_NW>(mx, s.red);
   return mx[0] < eps * nrm;
 }
 
@@ -616,7 +516,7 @@ __device__ __forceinline__ bool fq_dual_infeasible(FleetSmem &s, FleetRegs &R, d
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h)
     if (R.vok[h]) v[0] = fmax(v[0], fabs(R.D[h] * R.dx[h]));
-  fq_max<1>(v, s.red);
+  wg_max<1, FQ_NW>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double a[1] = {0.0}, pm[1] = {0.0};
@@ -626,8 +526,8 @@ __device__ __forceinline__ bool fq_dual_infeasible(FleetSmem &s, FleetRegs &R, d
       a[0] += R.q[h] * R.dx[h];
       pm[0] = fmax(pm[0], fabs(R.P[h] * R.dx[h] / R.D[h]));
     }
-  fq_sum<1>(a, s.red);
-  fq_max<1>(pm, s.red);
+  wg_sum<1, FQ_NW>(a, s.red);
+  wg_max<1, FQ_NW>(pm, s.red);
   if (!(a[0] < s.c * eps * nrm)) return false;
   if (!(pm[0] < s.c * eps * nrm)) return false;
 #pragma unroll
@@ -636,9 +536,7 @@ __device__ __forceinline__ bool fq_dual_infeasible(FleetSmem &s, FleetRegs &R, d
   __syncthreads();
   double bad[1] = {0.0};
   auto test = [&](double vv, double l, double u) {
-    if ((u < QP_OSQP_INFTY * QP_MIN_SCALING && vv > eps * nrm) ||
-        (l > -QP_OSQP_INFTY * QP_MIN_SCALING && vv < -eps * nrm))
-      bad[0] = 1.0;
+    if (qp_recedes_bad(vv, l, u, eps * nrm)) bad[0] = 1.0;
   };
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h) {
@@ -649,35 +547,8 @@ __device__ __forceinline__ bool fq_dual_infeasible(FleetSmem &s, FleetRegs &R, d
     }
     if (R.vok[h]) test((0.0 + R.Ab[h] * R.dx[h]) / s.E[FQ_MD + R.vj[h]], R.lb[h], R.ub[h]);
   }
-  fq_max<1>(bad, s.red);
+  wg_max<1, FQ_NW>(bad, s.red);
   return bad[0] == 0.0;
-}
-
-__device__ __forceinline__ bool fq_check(FleetSmem &s, FleetRegs &R, const QPSettingsDev &st, const double (&o)[8],
-                         bool approx, int &status) {
-  const double pri = o[0], dua = o[3] / s.c;
-  double ea = st.eps_abs, er = st.eps_rel, epi = st.eps_prim_inf, edi = st.eps_dual_inf;
-  if (pri > QP_OSQP_INFTY || dua > QP_OSQP_INFTY) {
-    status = -7;
-    return true;
-  }
-  if (approx) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-  bool prim_ok = false, prim_inf = false, dual_ok = false, dual_inf = false;
-  if (pri < ea + er * fmax(o[1], o[2])) prim_ok = true;
-  else prim_inf = fq_primal_infeasible(s, R, epi);
-  if (dua < ea + er * fmax(fmax(o[4], o[5]), o[6]) / s.c) dual_ok = true;
-  else dual_inf = fq_dual_infeasible(s, R, edi);
-  if (prim_ok && dual_ok) { status = approx ? 2 : 1; return true; }
-  if (prim_inf) { status = approx ? 3 : -3; return true; }
-  if (dual_inf) { status = approx ? 4 : -4; return true; }
-  return false;
-}
-
-__device__ __forceinline__ double fq_rho_estimate(const FleetSmem &s, const double (&re)[4]) {
-  const double pr = re[0] / (re[1] + 1e-10);
-  const double du = re[2] / (re[3] + 1e-10);
-  const double est = s.rho_s * sqrt(pr / (du + 1e-10));
-  return fmin(fmax(est, QP_RHO_MIN), QP_RHO_MAX);
 }
 
 __device__ __forceinline__ void fq_rebuild_zt(FleetSmem &s, FleetRegs &R) {
@@ -758,6 +629,8 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
   bool can_check = false;
   int it;
   double o[8], re[4];
+  auto prim_inf = [&](double eps) { return fq_primal_infeasible(s, R, eps); };
+  auto dual_inf = [&](double eps) { return fq_dual_infeasible(s, R, eps); };
   for (it = 1; it <= st.max_iter; ++it) {
 #if FQ_LAUNDER & 2
 #pragma unroll
@@ -772,7 +645,7 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
       for (int h = 0; h < FQ_H; ++h)
         if (R.vok[h]) {
           double acc = cd[h];
-          acc += R.Ab[h] * (fq_rho(R.lb[h], R.ub[h], s.rho_s) * R.zb_(h) - R.yb_(h));
+          acc += R.Ab[h] * (qp_row_rho(R.lb[h], R.ub[h], s.rho_s) * R.zb_(h) - R.yb_(h));
           s.rhs[R.vj[h]] = sig * R.x[h] - R.q[h] + acc;
         }
     }
@@ -781,7 +654,7 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
     for (int h = 0; h < FQ_H; ++h)
       if (R.vok[h]) {
         double acc = fq_col_dot(s, R, h);
-        acc += R.Ab[h] * (fq_rho(R.lb[h], R.ub[h], s.rho_s) * R.zb_(h) - R.yb_(h));
+        acc += R.Ab[h] * (qp_row_rho(R.lb[h], R.ub[h], s.rho_s) * R.zb_(h) - R.yb_(h));
         const double rv = sig * R.x[h] - R.q[h] + acc;
         s.rhs[R.vj[h]] = rv;
 #if FQ_PART
@@ -837,19 +710,13 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
 #else
         const double xt = s.rhs[R.vj[h]];
 #endif
-        const double xo = R.x[h];
-        const double xn = al * xt + (1.0 - al) * xo;
-        R.dx[h] = xn - xo;
-        R.x[h] = xn;
+        const QPXStep xs = qp_x_step(al, xt, R.x[h]);
+        R.dx[h] = xs.dx;
+        R.x[h] = xs.xn;
         // bound row: z~ = A_b x~_j
-        const double ztl = 0.0 + R.Ab[h] * xt;
-        const double rho = fq_rho(R.lb[h], R.ub[h], rs), zo = R.zb_(h), yo = R.yb_(h);
-        const double zr = al * ztl + (1.0 - al) * zo;
-        double zn = zr + yo / rho;
-        zn = fmin(fmax(zn, R.lb[h]), R.ub[h]);
-        const double d = rho * (zr - zn);
-        const double yn = yo + d;
-        R.dyb_(h) = d; R.yb_(h) = yn; R.zb_(h) = zn;
+        const QPRowStep b = qp_row_step(al, 0.0 + R.Ab[h] * xt, qp_row_rho(R.lb[h], R.ub[h], rs), R.lb[h], R.ub[h],
+                                        R.zb_(h), R.yb_(h));
+        R.dyb_(h) = b.dy; R.yb_(h) = b.yn; R.zb_(h) = b.zn;
       }
       if (R.rok[h]) {
 #if FQ_PART
@@ -857,29 +724,25 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
 #else
         const double ztl = fq_row_dot(s, R, h);
 #endif
-        const double rho = QP_RHO_EQ * rs, zo = R.zr(h), yo = R.yr(h);
-        const double zr = al * ztl + (1.0 - al) * zo;
-        double zn = zr + yo / rho;
-        zn = fmin(fmax(zn, R.ur(h)), R.ur(h));
-        const double d = rho * (zr - zn);
-        const double yn = yo + d;
-        R.dyr(h) = d; R.yr(h) = yn; R.zr(h) = zn;
-        s.zt[R.rr[h]] = rho * zn - yn;
+        const double rho = QP_RHO_EQ * rs;
+        const QPRowStep d = qp_row_step(al, ztl, rho, R.ur(h), R.ur(h), R.zr(h), R.yr(h));
+        R.dyr(h) = d.dy; R.yr(h) = d.yn; R.zr(h) = d.zn;
+        s.zt[R.rr[h]] = rho * d.zn - d.yn;
       }
     }
     T.mark(12);
     __syncthreads();
     T.mark(5);
-    can_check = st.check_termination && (it % st.check_termination == 0);
-    const bool adapt = st.adaptive_rho && st.adaptive_rho_interval && (it % st.adaptive_rho_interval == 0);
+    bool adapt;
+    qp_due(st, it, can_check, adapt);
     if (can_check || adapt) {
       res.iter = it;
       fq_update_info(s, R, o, re);
     }
-    if (can_check && fq_check(s, R, st, o, false, res.status)) break;
+    if (can_check && qp_terminated(o, s.c, st, false, res.status, prim_inf, dual_inf)) break;
     if (adapt) {
-      const double est = fq_rho_estimate(s, re);
-      if (est > s.rho_s * st.adaptive_rho_tolerance || est < s.rho_s / st.adaptive_rho_tolerance) {
+      const double est = qp_rho_estimate(re, s.rho_s);
+      if (qp_rho_moved(est, s.rho_s, st.adaptive_rho_tolerance)) {
         __syncthreads();
         if (tid == 0) s.rho_s = est;
         __syncthreads();
@@ -897,20 +760,20 @@ __device__ __forceinline__ QPResult fq_solve(const QPPattern &pt, FleetSmem &s, 
   if (!can_check) {
     res.iter = it - 1;
     fq_update_info(s, R, o, re);
-    fq_check(s, R, st, o, false, res.status);
+    qp_terminated(o, s.c, st, false, res.status, prim_inf, dual_inf);
   }
   if (res.status == -10) {
     // the residuals of the last check iteration, recomputed from the unchanged
     // iterates (rebuilding rho z - y touches none of them) so that o[] is not
     // live across the iteration loop (register pressure)
     if (can_check) fq_update_info(s, R, o, re);
-    if (!fq_check(s, R, st, o, true, res.status)) res.status = -2;
+    if (!qp_terminated(o, s.c, st, true, res.status, prim_inf, dual_inf)) res.status = -2;
   }
   double ob[1] = {0.0};
 #pragma unroll
   for (int h = 0; h < FQ_H; ++h)
     if (R.vok[h]) ob[0] += 0.5 * R.x[h] * (R.P[h] * R.x[h]) + R.q[h] * R.x[h];
-  fq_sum<1>(ob, s.red);
+  wg_sum<1, FQ_NW>(ob, s.red);
   res.obj = ob[0] / s.c;
   return res;
 }

@@ -18,24 +18,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <utility>
+#include "qp_rules.h"  // the iteration rules and constants shared with fleet_qp.h / fleet6_n.h
 
-#define QP_OSQP_INFTY 1e30
-#define QP_MIN_SCALING 1e-4
-#define QP_MAX_SCALING 1e4
-#define QP_RHO_MIN 1e-6
-#define QP_RHO_MAX 1e6
-#define QP_RHO_TOL 1e-4
-#define QP_RHO_EQ 1e3
-#define QP_DIV_TOL 1e-30
 #define QP_RMAX 8   // max entries per row of A (register-hoisted pattern)
 #define QP_CMAX 12  // max entries per column of A
-
-struct QPSettingsDev {
-  double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
-  int max_iter, check_termination, adaptive_rho, adaptive_rho_interval;
-  double adaptive_rho_tolerance;
-  int scaling, warm_start;
-};
 
 // shared sparsity pattern (device memory), prepared on the host once per batch
 struct QPPattern {
@@ -87,45 +73,8 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
   return __hiloint2double(hi, lo);
 }
 
-__device__ __forceinline__ double qp_limit(double v) {
-  v = v < QP_MIN_SCALING ? 1.0 : v;
-  return v > QP_MAX_SCALING ? QP_MAX_SCALING : v;
-}
-
-// block-wide max of K values (non-negative); every thread gets the result
-template <int K>
-__device__ void block_max(double (&v)[K], double (*red)[8]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = fmax(v[k], __shfl_xor(v[k], o));
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = fmax(fmax(red[0][k], red[1][k]), fmax(red[2][k], red[3][k]));
-  __syncthreads();
-}
-
-template <int K>
-__device__ void block_sum(double (&v)[K], double (*red)[8]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-  __syncthreads();
-}
+// the block's reductions: four waves, their partials combined pairwise (qp_rules.h)
+#define QP_NW 4
 
 // out[r] = (A x)[r]
 template <class S>
@@ -183,8 +132,8 @@ __device__ void qp_scale(const QPPattern &pt, S &s, int iters) {
     }
     double mx[1] = {0.0};
     for (int j = tid; j < n; j += nt) mx[0] = fmax(mx[0], fabs(s.q[j]));
-    block_sum<1>(v, s.red);
-    block_max<1>(mx, s.red);
+    wg_sum<1, QP_NW, true>(v, s.red);
+    wg_max<1, QP_NW, true>(mx, s.red);
     double ct = v[0] / n;
     const double nq = qp_limit(mx[0]);
     ct = qp_limit(fmax(ct, nq));
@@ -207,12 +156,7 @@ template <class S>
 __device__ void qp_set_rho(const QPPattern &pt, S &s) {
   const double rs = s.rho_s;
   for (int r = threadIdx.x; r < pt.m; r += blockDim.x) {
-    const double lr = s.l[r], ur = s.u[r];
-    double v;
-    if (lr < -QP_OSQP_INFTY * QP_MIN_SCALING && ur > QP_OSQP_INFTY * QP_MIN_SCALING) v = QP_RHO_MIN;
-    else if (ur - lr < QP_RHO_TOL) v = QP_RHO_EQ * rs;
-    else v = rs;
-    s.rho[r] = v;
+    s.rho[r] = qp_row_rho(s.l[r], s.u[r], rs);
   }
   __syncthreads();
 }
@@ -436,8 +380,7 @@ struct QPStamps {
 
 #include "qp_block.h"
 
-// residuals (auxil.c update_info): tmpm <- A x, aux <- P x, tmpn <- A' y.
-// o: 0 pri (unscaled)  1 |z/E|  2 |Ax/E|  3 dua*c  4 |q/D|  5 |A'y/D|  6 |Px/D|
+// residuals (auxil.c update_info): tmpm <- A x, aux <- P x, tmpn <- A' y; o[] as qp_acc_*
 template <class S>
 __device__ void qp_update_info(const QPPattern &pt, S &s, double (&o)[8]) {
   const int n = pt.n, m = pt.m, tid = threadIdx.x, nt = blockDim.x;
@@ -445,23 +388,12 @@ __device__ void qp_update_info(const QPPattern &pt, S &s, double (&o)[8]) {
   qp_spmv_t(pt, s, s.y, s.tmpn);
   for (int j = tid; j < n; j += nt) s.aux[j] = s.P[j] * s.x[j];
   __syncthreads();
-  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int r = tid; r < m; r += nt) {
-    const double e = s.E[r];
-    v[0] = fmax(v[0], fabs((s.tmpm[r] - s.z[r]) / e));
-    v[1] = fmax(v[1], fabs(s.z[r] / e));
-    v[2] = fmax(v[2], fabs(s.tmpm[r] / e));
-  }
-  for (int j = tid; j < n; j += nt) {
-    const double d = s.D[j];
-    v[3] = fmax(v[3], fabs((s.q[j] + s.aux[j] + s.tmpn[j]) / d));
-    v[4] = fmax(v[4], fabs(s.q[j] / d));
-    v[5] = fmax(v[5], fabs(s.tmpn[j] / d));
-    v[6] = fmax(v[6], fabs(s.aux[j] / d));
-  }
-  block_max<8>(v, s.red);
+  double v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r = tid; r < m; r += nt) qp_acc_row(v, s.tmpm[r], s.z[r], s.E[r]);
+  for (int j = tid; j < n; j += nt) qp_acc_var(v, s.q[j], s.aux[j], s.tmpn[j], s.D[j]);
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = v[k];
+  wg_max<8, QP_NW, true>(o, s.red);
 }
 
 template <class S>
@@ -471,28 +403,22 @@ __device__ bool qp_primal_infeasible(const QPPattern &pt, S &s, double eps) {
   const int n = pt.n, m = pt.m, tid = threadIdx.x, nt = blockDim.x;
   double v[1] = {0.0};
   for (int r = tid; r < m; r += nt) {
-    double d = s.dy[r];
-    const bool bu = s.u[r] > QP_OSQP_INFTY * QP_MIN_SCALING;
-    const bool bl = s.l[r] < -QP_OSQP_INFTY * QP_MIN_SCALING;
-    if (bu && bl) d = 0.0;
-    else if (bu) d = fmin(d, 0.0);
-    else if (bl) d = fmax(d, 0.0);
+    const double d = qp_polar(s.dy[r], s.l[r], s.u[r]);
     s.dy[r] = d;
     v[0] = fmax(v[0], fabs(s.E[r] * d));
   }
-  block_max<1>(v, s.red);
+  wg_max<1, QP_NW, true>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double sm[1] = {0.0};
-  for (int r = tid; r < m; r += nt)
-    sm[0] += s.u[r] * fmax(s.dy[r], 0.0) + s.l[r] * fmin(s.dy[r], 0.0);
-  block_sum<1>(sm, s.red);
+  for (int r = tid; r < m; r += nt) sm[0] += qp_support(s.dy[r], s.l[r], s.u[r]);
+  wg_sum<1, QP_NW, true>(sm, s.red);
   if (!(sm[0] < -eps * nrm)) return false;
   qp_spmv_t(pt, s, s.dy, s.rhs);  // rhs is free at check time
   __syncthreads();
   double mx[1] = {0.0};
   for (int j = tid; j < n; j += nt) mx[0] = fmax(mx[0], fabs(s.rhs[j] / s.D[j]));
-  block_max<1>(mx, s.red);
+  wg_max<1, QP_NW, true>(mx, s.red);
   return mx[0] < eps * nrm;
 }
 
@@ -501,71 +427,37 @@ __device__ bool qp_dual_infeasible(const QPPattern &pt, S &s, double eps) {
   const int n = pt.n, m = pt.m, tid = threadIdx.x, nt = blockDim.x;
   double v[1] = {0.0};
   for (int j = tid; j < n; j += nt) v[0] = fmax(v[0], fabs(s.D[j] * s.dx[j]));
-  block_max<1>(v, s.red);
+  wg_max<1, QP_NW, true>(v, s.red);
   const double nrm = v[0];
   if (!(nrm > QP_DIV_TOL)) return false;
   double a[1] = {0.0};
   for (int j = tid; j < n; j += nt) a[0] += s.q[j] * s.dx[j];
   double pm[1] = {0.0};
   for (int j = tid; j < n; j += nt) pm[0] = fmax(pm[0], fabs(s.P[j] * s.dx[j] / s.D[j]));
-  block_sum<1>(a, s.red);
-  block_max<1>(pm, s.red);
+  wg_sum<1, QP_NW, true>(a, s.red);
+  wg_max<1, QP_NW, true>(pm, s.red);
   if (!(a[0] < s.c * eps * nrm)) return false;
   if (!(pm[0] < s.c * eps * nrm)) return false;
   qp_spmv(pt, s, s.dx, s.zt);  // zt is rebuilt after every check
   __syncthreads();
   double bad[1] = {0.0};
-  for (int r = tid; r < m; r += nt) {
-    const double vv = s.zt[r] / s.E[r];
-    if ((s.u[r] < QP_OSQP_INFTY * QP_MIN_SCALING && vv > eps * nrm) ||
-        (s.l[r] > -QP_OSQP_INFTY * QP_MIN_SCALING && vv < -eps * nrm))
-      bad[0] = 1.0;
-  }
-  block_max<1>(bad, s.red);
+  for (int r = tid; r < m; r += nt)
+    if (qp_recedes_bad(s.zt[r] / s.E[r], s.l[r], s.u[r], eps * nrm)) bad[0] = 1.0;
+  wg_max<1, QP_NW, true>(bad, s.red);
   return bad[0] == 0.0;
 }
 
-// auxil.c check_termination; status values as OSQP 0.6
-template <class S>
-__device__ bool qp_check(const QPPattern &pt, S &s, const QPSettingsDev &st, const double (&o)[8],
-                         bool approx, int &status) {
-  const double pri = o[0], dua = o[3] / s.c;
-  double ea = st.eps_abs, er = st.eps_rel, epi = st.eps_prim_inf, edi = st.eps_dual_inf;
-  if (pri > QP_OSQP_INFTY || dua > QP_OSQP_INFTY) {
-    status = -7;
-    return true;
-  }
-  if (approx) { ea *= 10; er *= 10; epi *= 10; edi *= 10; }
-  bool prim_ok = false, prim_inf = false, dual_ok = false, dual_inf = false;
-  if (pri < ea + er * fmax(o[1], o[2])) prim_ok = true;
-  else prim_inf = qp_primal_infeasible(pt, s, epi);
-  if (dua < ea + er * fmax(fmax(o[4], o[5]), o[6]) / s.c) dual_ok = true;
-  else dual_inf = qp_dual_infeasible(pt, s, edi);
-  if (prim_ok && dual_ok) { status = approx ? 2 : 1; return true; }
-  if (prim_inf) { status = approx ? 3 : -3; return true; }
-  if (dual_inf) { status = approx ? 4 : -4; return true; }
-  return false;
-}
-
 // compute_rho_estimate in the scaled space, from qp_update_info's scratch
-// (tmpm = A x, aux = P x, tmpn = A' y)
+// (tmpm = A x, aux = P x, tmpn = A' y), in a reduction of its own
 template <class S>
 __device__ double qp_rho_estimate(const QPPattern &pt, S &s) {
   const int n = pt.n, m = pt.m, tid = threadIdx.x, nt = blockDim.x;
-  double v[6] = {0, 0, 0, 0, 0, 0};
-  for (int r = tid; r < m; r += nt) {
-    v[0] = fmax(v[0], fabs(s.tmpm[r] - s.z[r]));
-    v[1] = fmax(v[1], fmax(fabs(s.z[r]), fabs(s.tmpm[r])));
-  }
-  for (int j = tid; j < n; j += nt) {
-    v[2] = fmax(v[2], fabs(s.q[j] + s.aux[j] + s.tmpn[j]));
-    v[3] = fmax(v[3], fmax(fmax(fabs(s.q[j]), fabs(s.tmpn[j])), fabs(s.aux[j])));
-  }
-  block_max<6>(v, s.red);
-  const double pr = v[0] / (v[1] + 1e-10);
-  const double du = v[2] / (v[3] + 1e-10);
-  double est = s.rho_s * sqrt(pr / (du + 1e-10));
-  return fmin(fmax(est, QP_RHO_MIN), QP_RHO_MAX);
+  double v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r = tid; r < m; r += nt) qp_acc_row(v, s.tmpm[r], s.z[r], s.E[r]);
+  for (int j = tid; j < n; j += nt) qp_acc_var(v, s.q[j], s.aux[j], s.tmpn[j], s.D[j]);
+  double re[4] = {v[8], v[9], v[10], v[11]};
+  wg_max<4, QP_NW, true>(re, s.red);
+  return qp_rho_estimate(re, s.rho_s);
 }
 
 struct QPResult {
@@ -641,6 +533,8 @@ __device__ QPResult qp_solve(const QPPattern &pt, S &s, const QPSettingsDev &st,
   bool can_check = false;
   int it;
   double o[8];
+  auto prim_inf = [&](double eps) { return qp_primal_infeasible(pt, s, eps); };
+  auto dual_inf = [&](double eps) { return qp_dual_infeasible(pt, s, eps); };
   for (it = 1; it <= st.max_iter; ++it) {
     // rhs = sigma x - q + A'(rho z - y)
     if (tid < n) {
@@ -666,10 +560,12 @@ __device__ QPResult qp_solve(const QPPattern &pt, S &s, const QPSettingsDev &st,
     __syncthreads();
     T.mark(4);
     if (tid < n) {
+      // x is read before x~: the order of the two loads decides which product of the
+      // rule's sum the compiler contracts into an FMA, that is the last bit of x
       const double xo = s.x[tid];
-      const double xn = al * s.rhs[tid] + (1.0 - al) * xo;
-      s.dx[tid] = xn - xo;
-      s.x[tid] = xn;
+      const QPXStep xs = qp_x_step(al, s.rhs[tid], xo);
+      s.dx[tid] = xs.dx;
+      s.x[tid] = xs.xn;
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -679,26 +575,22 @@ __device__ QPResult qp_solve(const QPPattern &pt, S &s, const QPSettingsDev &st,
 #pragma unroll
         for (int e = 0; e < QP_RMAX; ++e)
           if (e < rn[h]) zt += s.A[rb[h] + e] * s.rhs[rc[h][e]];
-        const double rho = s.rho[r], zo = s.z[r], yo = s.y[r];
-        const double zr = al * zt + (1.0 - al) * zo;
-        double zn = zr + yo / rho;
-        zn = fmin(fmax(zn, s.l[r]), s.u[r]);
-        const double d = rho * (zr - zn);
-        const double yn = yo + d;
-        s.dy[r] = d;
-        s.y[r] = yn;
-        s.z[r] = zn;
-        s.zt[r] = rho * zn - yn;  // next iteration's A' operand
+        const double rho = s.rho[r];
+        const QPRowStep rs = qp_row_step(al, zt, rho, s.l[r], s.u[r], s.z[r], s.y[r]);
+        s.dy[r] = rs.dy;
+        s.y[r] = rs.yn;
+        s.z[r] = rs.zn;
+        s.zt[r] = rho * rs.zn - rs.yn;  // next iteration's A' operand
       }
     }
     __syncthreads();
     T.mark(5);
-    can_check = st.check_termination && (it % st.check_termination == 0);
-    const bool adapt = st.adaptive_rho && st.adaptive_rho_interval && (it % st.adaptive_rho_interval == 0);
+    bool adapt;
+    qp_due(st, it, can_check, adapt);
     if (can_check) {
       res.iter = it;
       qp_update_info(pt, s, o);
-      if (qp_check(pt, s, st, o, false, res.status)) break;
+      if (qp_terminated(o, s.c, st, false, res.status, prim_inf, dual_inf)) break;
     }
     if (adapt) {
       if (!can_check) {
@@ -706,7 +598,7 @@ __device__ QPResult qp_solve(const QPPattern &pt, S &s, const QPSettingsDev &st,
         qp_update_info(pt, s, o);
       }
       const double est = qp_rho_estimate(pt, s);
-      if (est > s.rho_s * st.adaptive_rho_tolerance || est < s.rho_s / st.adaptive_rho_tolerance) {
+      if (qp_rho_moved(est, s.rho_s, st.adaptive_rho_tolerance)) {
         __syncthreads();
         if (tid == 0) s.rho_s = est;
         __syncthreads();
@@ -728,15 +620,15 @@ __device__ QPResult qp_solve(const QPPattern &pt, S &s, const QPSettingsDev &st,
   if (!can_check) {
     res.iter = it - 1;
     qp_update_info(pt, s, o);
-    qp_check(pt, s, st, o, false, res.status);
+    qp_terminated(o, s.c, st, false, res.status, prim_inf, dual_inf);
   }
   if (res.status == -10) {
-    if (!qp_check(pt, s, st, o, true, res.status)) res.status = -2;
+    if (!qp_terminated(o, s.c, st, true, res.status, prim_inf, dual_inf)) res.status = -2;
   }
   // objective (1/c)(1/2 x'Px + q'x)
   double ob[1] = {0.0};
   for (int j = tid; j < n; j += nt) ob[0] += 0.5 * s.x[j] * (s.P[j] * s.x[j]) + s.q[j] * s.x[j];
-  block_sum<1>(ob, s.red);
+  wg_sum<1, QP_NW, true>(ob, s.red);
   res.obj = ob[0] / s.c;
   return res;
 }
