@@ -154,6 +154,10 @@ _sig("gpmpc_uprop3_linear", _c, _vp, _vp, _c, _c, ctypes.c_double, ctypes.c_doub
      ctypes.c_double, _dp, _dp)
 _sig("gpmpc_uprop6_linear", _c, _vp, _vp, _vp, _c, _dp, _c, _c, ctypes.c_double, _dp, _dp, _vp,
      ctypes.c_double, _dp, _dp)
+_sig("gpmpc_uprop3_unscented", _c, _vp, _vp, _c, _c, _c, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _dp,
+     _vp, ctypes.c_double, _dp, _dp, _ip)
+_sig("gpmpc_uprop6_unscented", _c, _vp, _vp, _vp, _c, _dp, _dp, _c, _c, ctypes.c_double, _dp, _dp, _vp,
+     ctypes.c_double, _dp, _dp, _ip)
 _sig("gpmpc_fleet_read", _c, _vp, _dp, _dp)
 _sig("gpmpc_gram_grad", _c, _vp, _c, _dp, _c, _dp, _c, _c, _dp, ctypes.c_double, _dp, _dp)
 _sig("gpmpc_fleet_get_state", _c, _vp, _dp, _dp, _dp, _dp)
@@ -216,7 +220,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
-            "gpmpc_tri_diag"]
+            "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented"]
 
 
 class HIPError(RuntimeError):
@@ -699,6 +703,49 @@ def uprop6_linear(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, s0_diag=1e
     _chk(_L.gpmpc_uprop6_linear(ctx.h, hv.h, hw.h, int(bool(exact)), _d(rk), B, N, float(dt), _d(X0), _d(U), s0,
                                 float(s0_diag), _d(means), _d(covs)), "uprop6_linear")
     return means, covs
+
+
+def _ut_buffers(what, nx, X0, U, S0, ut):
+    X0 = f64(np.atleast_2d(X0)); U = f64(U)
+    B, N = U.shape[0], U.shape[1]
+    if X0.shape != (B, nx) or U.shape != (B, N, 3):
+        raise ValueError(f"{what}: shapes X0 {X0.shape}, U {U.shape}")
+    s0 = None
+    if S0 is not None:
+        S0 = f64(S0)
+        if S0.shape != (B, nx, nx):
+            raise ValueError(f"{what}: S0 shape {S0.shape}")
+        s0 = S0.ctypes.data_as(_vp)
+    ut3 = f64(np.asarray(ut, float).reshape(3))
+    return X0, U, S0, s0, ut3, np.empty((B, N + 1, nx)), np.empty((B, N + 1, nx, nx)), np.zeros(B, np.int32)
+
+
+def uprop3_unscented(ctx, gp, exact, X0, U, S0=None, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0),
+                     ut=(1e-3, 2.0, 0.0), s0_diag=1e-6):
+    """gpmpc_uprop3_unscented: the 3-DoF unscented uncertainty propagation of B trajectories
+    on the device.  gp: the 3-DoF GP's ExactGPHandle (exact=True) or FITCHandle; ut: the
+    transform's (alpha, beta, kappa); X0 (B, 7), U (B, N, 3), S0 None or (B, 7, 7) -> means
+    (B, N+1, 7), covariances (B, N+1, 7, 7), info (B,): 0, or k+1 when the Cholesky factor of
+    step k failed (that trajectory's later rows are NaN)."""
+    X0, U, S0, s0, ut3, means, covs, info = _ut_buffers("uprop3_unscented", 7, X0, U, S0, ut)
+    g3 = f64(np.asarray(g, float).reshape(3))
+    _chk(_L.gpmpc_uprop3_unscented(ctx.h, gp.h, int(bool(exact)), U.shape[0], U.shape[1], float(dt), float(alpha),
+                                   _d(g3), _d(ut3), _d(X0), _d(U), s0, float(s0_diag), _d(means), _d(covs),
+                                   _i(info)), "uprop3_unscented")
+    return means, covs, info
+
+
+def uprop6_unscented(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, ut=(1e-3, 2.0, 0.0), s0_diag=1e-6):
+    """gpmpc_uprop6_unscented: the 14-state unscented uncertainty propagation of B
+    trajectories on the device.  hv, hw, exact, rocket as uprop6_linear; ut: the transform's
+    (alpha, beta, kappa); X0 (B, 14), U (B, N, 3), S0 None or (B, 14, 14) -> means
+    (B, N+1, 14), covariances (B, N+1, 14, 14), info (B,) as uprop3_unscented."""
+    X0, U, S0, s0, ut3, means, covs, info = _ut_buffers("uprop6_unscented", 14, X0, U, S0, ut)
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    _chk(_L.gpmpc_uprop6_unscented(ctx.h, hv.h, hw.h, int(bool(exact)), _d(rk), _d(ut3), U.shape[0], U.shape[1],
+                                   float(dt), _d(X0), _d(U), s0, float(s0_diag), _d(means), _d(covs), _i(info)),
+         "uprop6_unscented")
+    return means, covs, info
 
 
 def cov_propagate(ctx, A, q, S0=None, s0_diag=1e-6):

@@ -13,6 +13,13 @@ batched over trajectories in ``propagate_batch`` -- and its covariance
 recursion Sigma_{k+1} = A_k Sigma_k A_k^T + Q_k runs for every trajectory in
 one launch of the device kernel (``gpmpc_cov_propagate``, csrc/uprop.hip).
 
+The unscented method runs its whole recursion -- Cholesky factor, sigma points,
+model step, GP means and the variance at the centre -- in one device call for a
+batch of trajectories (``propagate_unscented_batch``; ``gpmpc_uprop3_unscented`` /
+``gpmpc_uprop6_unscented``, csrc/uprop_ut.hip) where the linear device paths'
+gates accept, and the per-step host loop elsewhere.  Monte-Carlo propagation is
+host numpy (it consumes the global RNG in the reference's draw order).
+
 Both model shapes work: the reference's 14-state 6-DoF model with a 4-tuple GP
 (StructuredRocketGP: residuals on v-dot 4:7 and omega-dot 11:14), and the
 7-state 3-DoF model with a 2-tuple GP (Simple3DoFGP: residual on v-dot only).
@@ -94,10 +101,11 @@ class UncertaintyPropagator:
     # host loop below become one kernel; the same recursion, rounding aside
     use_device = True
 
-    def _device_6dof(self, X0, U, Sigma_0, dt):
-        """gpmpc_uprop6_linear for Rocket6DoFDynamics over a fitted StructuredRocketGP at its
-        default feature set (the device features are features.py's at reference velocity
-        10 with altitude and density), its residual groups each one shared device GP."""
+    def _gate_6dof(self):
+        """(hv, hw, exact, rocket) when the 14-state device recursions apply:
+        Rocket6DoFDynamics over a fitted StructuredRocketGP at its default feature set (the
+        device features are features.py's at reference velocity 10 with altitude and
+        density), its residual groups each one shared device GP.  Else None."""
         if not self.use_device or self.n_x != 14:
             return None
         from ..dynamics.rocket_6dof import Rocket6DoFDynamics
@@ -115,36 +123,56 @@ class UncertaintyPropagator:
         rocket = np.concatenate([np.asarray(p.J_B, float).reshape(9), np.asarray(p.r_T_B, float).reshape(3),
                                  np.asarray(p.g_I, float).reshape(3),
                                  [float(p.alpha), float(p.g0)]])
+        return hv, hw, not c.use_sparse, rocket
+
+    def _device_6dof(self, X0, U, Sigma_0, dt):
+        """gpmpc_uprop6_linear where _gate_6dof accepts."""
+        gate = self._gate_6dof()
+        if gate is None:
+            return None
+        hv, hw, exact, rocket = gate
         S0 = None
         if Sigma_0 is not None:
             S0 = np.broadcast_to(np.asarray(Sigma_0, float), (X0.shape[0], 14, 14))
         try:
-            return _lib.uprop6_linear(self.ctx, hv, hw, not c.use_sparse, rocket, X0, U, S0, dt)
+            return _lib.uprop6_linear(self.ctx, hv, hw, exact, rocket, X0, U, S0, dt)
         except _lib.HIPError:
             return None   # (a composite-kernel GP: the host loop)
 
-    def _device_3dof(self, X0, U, Sigma_0, dt):
+    def _gate_3dof(self, sparse_ok=False):
+        """(handle, exact) when the 3-DoF device recursions apply: Rocket3DoFDynamics over a
+        fitted Simple3DoFGP with a device handle -- the exact GP's, or with sparse_ok the
+        shared FITC one (the linear recursion takes a gpmpc_gp only).  Else None."""
         if not self.use_device or self.n_x != 7:
             return None
         from ..dynamics.rocket_3dof import Rocket3DoFDynamics
         from ..gp.exact_gp import MultiOutputExactGP
         from ..gp.features import Simple3DoFFeatureExtractor
+        from ..gp.sparse_gp import MultiOutputSparseGP
         gp = self.gp
         inner = getattr(gp, "gp", None)
-        # (only the exact GP's handle is a gpmpc_gp; a FITC handle is another type)
-        if (type(self.dynamics) is not Rocket3DoFDynamics or not isinstance(inner, MultiOutputExactGP)
+        exact = isinstance(inner, MultiOutputExactGP)
+        if (type(self.dynamics) is not Rocket3DoFDynamics
+                or not (exact or (sparse_ok and isinstance(inner, MultiOutputSparseGP)))
                 or type(getattr(gp, "feature_extractor", None)) is not Simple3DoFFeatureExtractor
                 or not getattr(gp, "_is_fitted", False)):
             return None
         h = inner.device_handle
         if h is None:
             return None
+        return h, exact
+
+    def _device_3dof(self, X0, U, Sigma_0, dt):
+        # (only the exact GP's handle is a gpmpc_gp; a FITC handle is another type)
+        gate = self._gate_3dof()
+        if gate is None:
+            return None
         p = self.dynamics.params
         S0 = None
         if Sigma_0 is not None:
             S0 = np.broadcast_to(np.asarray(Sigma_0, float), (X0.shape[0], 7, 7))
         try:
-            return _lib.uprop3_linear(self.ctx, h, X0, U, S0, dt, float(p.alpha), np.asarray(p.g_vec, float))
+            return _lib.uprop3_linear(self.ctx, gate[0], X0, U, S0, dt, float(p.alpha), np.asarray(p.g_vec, float))
         except _lib.HIPError:
             return None   # (a composite-kernel GP: the host loop)
 
@@ -202,14 +230,78 @@ class UncertaintyPropagator:
         return means, covs
 
     # --------------------------------------------------------------- unscented
+    # the transform's (alpha, beta, kappa): the reference's constants (uncertainty_prop.py:196-198)
+    ut_params = (1e-3, 2.0, 0.0)
+
     def _propagate_unscented(self, x0, U, Sigma_0, dt) -> PropagatedUncertainty:
+        """uncertainty_prop.py:179-264 for one trajectory (a batch of one)."""
+        S0 = None if Sigma_0 is None else np.asarray(Sigma_0, float)[None]
+        U = np.atleast_2d(np.asarray(U, float))
+        means, covs = self.propagate_unscented_batch(np.asarray(x0, float)[None], U[None], S0, dt)
+        return PropagatedUncertainty(means=means[0], covariances=covs[0])
+
+    def _device_unscented(self, X0, U, S0, dt):
+        """The whole unscented recursion of every trajectory in one device call
+        (gpmpc_uprop3_unscented / gpmpc_uprop6_unscented, csrc/uprop_ut.hip) where the gates
+        of the linear device paths accept -- and for the 3-DoF model a sparse GP too.
+        (means, covs, info), or None: the host loop."""
+        try:
+            gate = self._gate_3dof(sparse_ok=True)
+            if gate is not None:
+                p = self.dynamics.params
+                return _lib.uprop3_unscented(self.ctx, gate[0], gate[1], X0, U, S0, dt, float(p.alpha),
+                                             np.asarray(p.g_vec, float), self.ut_params)
+            gate = self._gate_6dof()
+            if gate is not None:
+                hv, hw, exact, rocket = gate
+                return _lib.uprop6_unscented(self.ctx, hv, hw, exact, rocket, X0, U, S0, dt, self.ut_params)
+        except _lib.HIPError:
+            pass   # (a composite-kernel GP: the host loop)
+        return None
+
+    def propagate_unscented_batch(self, X0, U, Sigma_0=None, dt: float = 0.1):
+        """Unscented propagation of B trajectories at once.
+
+        X0 (B, n_x), U (B, N, n_u), Sigma_0 None (the reference's 1e-6 I), (n_x, n_x) or
+        (B, n_x, n_x) -> means (B, N+1, n_x), covariances (B, N+1, n_x, n_x).  One device
+        call where _device_unscented accepts, else the host loop once per trajectory.  A
+        covariance whose scaled Cholesky factor does not exist raises np.linalg.LinAlgError
+        on either path."""
+        X0 = np.atleast_2d(np.asarray(X0, float)); U = np.asarray(U, float)
+        if U.ndim == 2:
+            U = U[None]
+        B, N = U.shape[0], U.shape[1]
+        nx = self.n_x
+        if X0.shape != (B, nx):
+            raise ValueError(f"X0 shape {X0.shape}, expected {(B, nx)}")
+        S0 = None
+        if Sigma_0 is not None:
+            S0 = np.asarray(Sigma_0, float)
+            if S0.shape not in ((nx, nx), (B, nx, nx)):
+                raise ValueError(f"Sigma_0 shape {S0.shape}, expected {(nx, nx)} or {(B, nx, nx)}")
+            S0 = np.broadcast_to(S0, (B, nx, nx))
+        dev = self._device_unscented(X0, U, S0, dt)
+        if dev is not None:
+            means, covs, info = dev
+            bad = np.flatnonzero(info)
+            if bad.size:
+                b = int(bad[0])
+                raise np.linalg.LinAlgError(f"unscented propagation: trajectory {b}, step {int(info[b]) - 1}: "
+                                            "the scaled covariance is not positive definite")
+            return means, covs
+        means = np.zeros((B, N + 1, nx)); covs = np.zeros((B, N + 1, nx, nx))
+        for b in range(B):
+            means[b], covs[b] = self._unscented_host(X0[b], U[b], None if S0 is None else S0[b], dt)
+        return means, covs
+
+    def _unscented_host(self, x0, U, Sigma_0, dt):
         """uncertainty_prop.py:179-264; the 2n+1 sigma points and the mean point
         of a step go to the GP as one batch."""
-        U = np.atleast_2d(np.asarray(U, float))
+        U = np.atleast_2d(np.asarray(U, float)).reshape(-1, 3)
         N, n = len(U), self.n_x
         if Sigma_0 is None:
             Sigma_0 = np.eye(n) * 1e-6
-        alpha, beta, kappa = 1e-3, 2, 0
+        alpha, beta, kappa = self.ut_params
         lam = alpha ** 2 * (n + kappa) - n
         w_m = np.full(2 * n + 1, 1 / (2 * (n + lam)))
         w_c = w_m.copy()
@@ -245,7 +337,7 @@ class UncertaintyPropagator:
             S_next += Q
             means[k + 1] = x_next; covs[k + 1] = S_next
             x_k, S_k = x_next, S_next
-        return PropagatedUncertainty(means=means, covariances=covs)
+        return means, covs
 
     # ------------------------------------------------------------- Monte Carlo
     def _propagate_monte_carlo(self, x0, U, Sigma_0, dt, n_samples: int = 100) -> PropagatedUncertainty:

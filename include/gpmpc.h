@@ -512,6 +512,30 @@ int gpmpc_uprop3_linear(gpmpc_ctx *ctx, gpmpc_gp *gp, int batch, int N, double d
 int gpmpc_uprop6_linear(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact, const double *rocket,
                         int batch, int N, double dt, const double *x0, const double *U,
                         const double *S0, double s0_diag, double *means, double *covs);
+/* UncertaintyPropagator._propagate_unscented (uncertainty_prop.py:179-264) of the 3-DoF
+ * model on the device, for batch trajectories in one call: per step the Cholesky factor of
+ * (n + lambda) Sigma_k + 1e-10 I, the 15 sigma points through the explicit-Euler step plus
+ * dt times the GP mean on the velocity rows, x_k+1 = sum w_m,i of their images, Sigma_k+1 =
+ * sum w_c,i d_i d_i^T + dt^2 times the GP variance at x_k on the velocity rows.  One
+ * workgroup per trajectory runs the whole recursion (csrc/uprop_ut.hip).  gp: gpmpc_gp *
+ * (exact = 1) or gpmpc_fitc * (exact = 0; FITC and VFE), 11 features, 3 outputs, a leaf
+ * kernel, at most 4096 training / inducing rows (else -2).  ut: the transform's alpha, beta,
+ * kappa (the reference: 1e-3, 2, 0).  dt, alpha, g3, x0, U, S0, s0_diag, means, covs as
+ * gpmpc_uprop3_linear.  info (batch, host): 0, or k + 1 when the factor of step k met a
+ * non-positive pivot -- that trajectory stops there, its rows k+1 .. N of means and covs
+ * are NaN, the others are unaffected and the call still returns 0.  (ABI 4: an added
+ * entry point.) */
+int gpmpc_uprop3_unscented(gpmpc_ctx *ctx, void *gp, int exact, int batch, int N, double dt, double alpha,
+                           const double *g3, const double *ut, const double *x0, const double *U,
+                           const double *S0, double s0_diag, double *means, double *covs, int *info);
+/* The same for the 14-state model: 29 sigma points through RK4 with quaternion
+ * normalisation (rocket_6dof.py step) plus dt times the StructuredRocketGP means on rows
+ * 4-6 (d_v) and 11-13 (d_omega), the variances of both GPs at x_k on those rows.  gp_v /
+ * gp_w, exact, rocket and the host buffers as gpmpc_uprop6_linear; ut and info as
+ * gpmpc_uprop3_unscented.  (ABI 4: an added entry point.) */
+int gpmpc_uprop6_unscented(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact, const double *rocket,
+                           const double *ut, int batch, int N, double dt, const double *x0, const double *U,
+                           const double *S0, double s0_diag, double *means, double *covs, int *info);
 
 /* ---- BASELINE configs[4]: batched 6-DoF GP-MPC rollouts --------------------
  * gpmpc_rollout_batched of SURVEY 8b.  One step = for every running rollout:

@@ -1,0 +1,368 @@
+"""The unscented uncertainty propagation in one device call (gpmpc_uprop3_unscented /
+gpmpc_uprop6_unscented, csrc/uprop_ut.hip) against the numpy restatement
+(tests/uprop_ut_check.py over oracle.uprop_oracle) and against the per-step host loop over
+the same device GPs.
+
+Sharp cases run the transform at ut_params = (1, 2, 0): lambda = 0, the weights are O(1)
+and two float64 evaluations of the recursion agree to ~1e-13, so the tolerances are those
+the linear device path meets (test_gpu_uprop.py).  At the reference's alpha = 1e-3 the
+centre weight is ~ -1e6 and the order of a sum alone moves the means by ~5e-7 (F9,
+test_uprop_ut_check.py); those cases carry the F9 bounds scaled by the magnitudes the
+weight multiplies."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import golden
+
+pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+
+SHARP = (1.0, 2.0, 0.0)
+REFERENCE = (1e-3, 2.0, 0.0)
+
+
+def _ctx_default(gpu_ctx):
+    from gp_mpc_rocket_landing_amd import _lib
+    _lib._default_ctx = gpu_ctx
+
+
+def _spread(rs, B, n, scale):
+    L = rs.randn(B, n, n) * scale
+    return np.einsum("bij,bkj->bik", L, L)
+
+
+# ---- the GPs and the models, fitted once ----------------------------------------------
+@pytest.fixture(scope="module")
+def f1():
+    return golden("f1_exact_simple3dof.npz")
+
+
+@pytest.fixture(scope="module")
+def gp3_exact(gpu_ctx, f1):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    gp = Simple3DoFGP(use_sparse=False)
+    gp.add_data(f1["X"], f1["U"], f1["D"]); gp.fit()
+    return gp
+
+
+@pytest.fixture(scope="module")
+def gp3_fitc(gpu_ctx, f1):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    np.random.seed(0)                       # (the inducing points: kmeans2 on the global RNG)
+    gp = Simple3DoFGP()                     # the reference default: FITC, 50 inducing points
+    gp.add_data(f1["X"], f1["U"], f1["D"]); gp.fit()
+    return gp
+
+
+@pytest.fixture(scope="module")
+def gps6(gpu_ctx):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.rollouts6 import fit_structured_gp
+    return {True: fit_structured_gp(300, 50, seed=0, use_sparse=True),
+            False: fit_structured_gp(300, 50, seed=0, use_sparse=False)}
+
+
+def _inputs3(f1, B, N, seed, first=0):
+    rs = np.random.RandomState(seed)
+    X0 = f1["X"][first:first + B] + 0.01 * rs.randn(B, 7)
+    U = np.repeat(f1["U"][first:first + B, None, :], N, axis=1) * (1 + 0.05 * rs.randn(B, N, 1))
+    return X0, U, rs
+
+
+def _inputs6(B, N, seed):
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig
+    from gp_mpc_rocket_landing_amd.rollouts6 import initial_conditions_6dof
+    rs = np.random.RandomState(seed)
+    X0 = initial_conditions_6dof(B)
+    X0[:, 11:14] = np.array([0.02, -0.01, 0.03])
+    U = np.zeros((B, N, 3))
+    U[:, :, 2] = 0.9 * X0[:, 0:1] * Rocket6DoFConfig().g0
+    U[:, :, :2] = 0.05 * rs.randn(B, N, 2)
+    return X0, U, rs
+
+
+def _dyn6(full_j):
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig, Rocket6DoFDynamics
+    rc = Rocket6DoFConfig()
+    if full_j:
+        J = np.array(rc.J_B, float)
+        J = J + 0.05 * np.sqrt(np.outer(np.diag(J), np.diag(J))) * np.array([[0, 1, -1], [1, 0, 0.5], [-1, 0.5, 0]])
+        rc = Rocket6DoFConfig(J_B=J)
+    return Rocket6DoFDynamics(rc)
+
+
+def _propagator(dyn, gp, gpu_ctx, ut):
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    p = UncertaintyPropagator(dyn, gp, method="unscented", ctx=gpu_ctx)
+    p.ut_params = ut
+    return p
+
+
+def _device_and_host(p, X0, U, S0, monkeypatch):
+    """(device means, covs), (host-loop means, covs): exactly one device call for the first,
+    none for the second."""
+    from gp_mpc_rocket_landing_amd import _lib
+    calls = []
+    name = "uprop3_unscented" if p.n_x == 7 else "uprop6_unscented"
+    real = getattr(_lib, name)
+    monkeypatch.setattr(_lib, name, lambda *a, **k: calls.append(1) or real(*a, **k))
+    md, cd = p.propagate_unscented_batch(X0, U, S0, 0.1)
+    assert len(calls) == 1, "the device path was not taken"
+    p.use_device = False
+    try:
+        mh, ch = p.propagate_unscented_batch(X0, U, S0, 0.1)
+    finally:
+        p.use_device = True
+    assert len(calls) == 1
+    B, N, n = U.shape[0], U.shape[1], p.n_x
+    assert md.shape == (B, N + 1, n) and cd.shape == (B, N + 1, n, n)
+    np.testing.assert_array_equal(md[:, 0], X0)
+    return (md, cd), (mh, ch)
+
+
+def _assert_sharp(dev, host, what):
+    (md, cd), (mh, ch) = dev, host
+    print(f"{what}: device vs host loop: means {np.abs(md - mh).max():.3e}, covs {np.abs(cd - ch).max():.3e} "
+          f"(rel {np.abs(cd - ch).max() / np.abs(ch).max():.3e})")
+    np.testing.assert_allclose(md, mh, rtol=0, atol=1e-10)
+    np.testing.assert_allclose(cd, ch, rtol=1e-7, atol=1e-15)
+
+
+def _assert_not_linear(p, X0, U, S0, md, what):
+    """The transform has not degenerated to the linear recursion on these inputs."""
+    ml, _ = p.propagate_batch(X0, U, S0, 0.1)
+    gap = np.abs(md - ml).max()
+    print(f"{what}: unscented vs linear means {gap:.3e}")
+    assert gap > 1e-6
+
+
+# ---- sharp cases: ut_params = (1, 2, 0), B = 3, N = 8, S0 = L L^T, L = 1e-2 randn ------
+def test_sharp_3dof_exact_vs_restatement(gpu_ctx, gp3_exact, f1):
+    """3-DoF exact GP on F1 (n = 1000) against the restatement over simple3dof_exact_predictor,
+    at the tolerances the linear device path meets against the same oracle."""
+    _ctx_default(gpu_ctx)
+    import uprop_ut_check
+    from oracle import uprop_oracle
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    dyn = create_normalized_rocket()
+    X0, U, rs = _inputs3(f1, 3, 8, 11)
+    S0 = _spread(rs, 3, 7, 1e-2)
+    p = _propagator(dyn, gp3_exact, gpu_ctx, SHARP)
+    md, cd = p.propagate_unscented_batch(X0, U, S0, 0.1)
+    orc = uprop_oracle.simple3dof_exact_predictor(f1["X"], f1["U"], f1["D"])
+    for b in range(3):
+        m, c = uprop_ut_check.propagate_unscented(dyn, orc, X0[b], U[b], S0[b], 0.1, SHARP)
+        print(f"3-DoF exact vs restatement, trajectory {b}: means {np.abs(md[b] - m).max():.3e}, "
+              f"covs rel {np.abs(cd[b] - c).max() / np.abs(c).max():.3e}")
+        np.testing.assert_allclose(md[b], m, rtol=1e-9, atol=1e-10)
+        np.testing.assert_allclose(cd[b], c, rtol=1e-6, atol=1e-14)
+    _assert_not_linear(p, X0, U, S0, md, "3-DoF exact")
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["exact", "default-fitc"])
+def test_sharp_3dof_device_vs_host_loop(gpu_ctx, monkeypatch, gp3_exact, gp3_fitc, f1, sparse):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    X0, U, rs = _inputs3(f1, 3, 8, 12)
+    S0 = _spread(rs, 3, 7, 1e-2)
+    p = _propagator(create_normalized_rocket(), gp3_fitc if sparse else gp3_exact, gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    _assert_sharp(dev, host, f"3-DoF sparse={sparse}")
+    if not sparse:   # (the linear device recursion takes the exact GP only)
+        _assert_not_linear(p, X0, U, S0, dev[0], "3-DoF exact")
+    else:
+        p.use_device = False
+        _assert_not_linear(p, X0, U, S0, dev[0], "3-DoF FITC")
+
+
+@pytest.mark.parametrize("sparse,full_j", [(True, False), (False, False), (True, True)],
+                         ids=["fitc-M50-rows-in-registers", "exact-n300-rows-read-per-step", "fitc-full-inertia"])
+def test_sharp_6dof_device_vs_host_loop(gpu_ctx, monkeypatch, gps6, sparse, full_j):
+    _ctx_default(gpu_ctx)
+    X0, U, rs = _inputs6(3, 8, 13)
+    S0 = _spread(rs, 3, 14, 1e-2)
+    p = _propagator(_dyn6(full_j), gps6[sparse], gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    _assert_sharp(dev, host, f"14-state sparse={sparse} full_j={full_j}")
+    _assert_not_linear(p, X0, U, S0, dev[0], "14-state")
+
+
+# ---- the reference's constants (alpha = 1e-3) ------------------------------------------
+def _assert_reference(dev, host, X0, what):
+    (md, cd), (mh, ch) = dev, host
+    am = 2e-6 * max(1.0, np.abs(X0).max() / 20.0)
+    ac = 1e-9 * max(1.0, np.abs(ch).max() / 6.9e-4)
+    print(f"{what}: device vs host loop at alpha = 1e-3: means {np.abs(md - mh).max():.3e} (bound {am:.3e}), "
+          f"covs {np.abs(cd - ch).max():.3e} (bound {ac:.3e})")
+    np.testing.assert_allclose(md, mh, rtol=0, atol=am)
+    np.testing.assert_allclose(cd, ch, rtol=0, atol=ac)
+
+
+@pytest.mark.parametrize("s0", [False, True], ids=["default-sigma0", "dense-sigma0"])
+def test_reference_constants_3dof(gpu_ctx, monkeypatch, gp3_exact, f1, s0):
+    """F9's bounds (2e-6 / 1e-9, about 4x the noise measured there) scaled by what the -1e6
+    weight multiplies: max |x0| against F9's 20, max |Sigma| against F9's 6.9e-4."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    X0, U, rs = _inputs3(f1, 2, 10, 21)
+    S0 = None
+    if s0:
+        S0 = _spread(rs, 2, 7, 2.5e-3)
+        S0 *= min(1.0, 1e-4 / np.abs(S0).max())
+    p = _propagator(create_normalized_rocket(), gp3_exact, gpu_ctx, REFERENCE)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    _assert_reference(dev, host, X0, "3-DoF exact")
+
+
+@pytest.mark.parametrize("sparse", [True, False], ids=["fitc", "exact"])
+def test_reference_constants_6dof(gpu_ctx, monkeypatch, gps6, sparse):
+    _ctx_default(gpu_ctx)
+    X0, U, rs = _inputs6(2, 8, 22)
+    S0 = None
+    if not sparse:
+        S0 = _spread(rs, 2, 14, 2e-3)
+        S0 *= min(1.0, 1e-4 / np.abs(S0).max())
+    p = _propagator(_dyn6(False), gps6[sparse], gpu_ctx, REFERENCE)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    _assert_reference(dev, host, X0, f"14-state sparse={sparse}")
+
+
+# ---- every branch on the training / inducing count -------------------------------------
+# (the pass over W = L^-1 for the variance reads 16-byte pairs when the row count is even and
+# single doubles when it is odd: a branch on the count too)
+@pytest.mark.parametrize("n", [999, 1000, 1100], ids=["n999-rows-in-registers-odd-count-W-by-doubles",
+                                                      "n1000-rows-in-registers-even-count-W-by-pairs",
+                                                      "n1100-rows-read-per-step"])
+def test_size_branch_3dof(gpu_ctx, monkeypatch, n):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.data import synthetic_training_data
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.fleet import initial_conditions
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    X, U, D = synthetic_training_data(n, seed=1)
+    gp = Simple3DoFGP(use_sparse=False)
+    gp.add_data(X, U, D); gp.fit()
+    X0 = initial_conditions(2)
+    rs = np.random.RandomState(n)
+    Uh = np.tile((-X0[:, 0:1] * np.array([-1.0, 0, 0]))[:, None, :], (1, 4, 1)) * (1 + 0.1 * rs.randn(2, 4, 1))
+    p = _propagator(create_normalized_rocket(), gp, gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, Uh, _spread(rs, 2, 7, 1e-2), monkeypatch)
+    _assert_sharp(dev, host, f"3-DoF n={n}")
+
+
+@pytest.mark.parametrize("M", [49, 256, 288], ids=["fitc-M49-odd-count-W-by-doubles", "fitc-M256-rows-in-registers",
+                                                   "fitc-M288-rows-read-per-step"])
+def test_size_branch_6dof_fitc(gpu_ctx, monkeypatch, M):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.rollouts6 import fit_structured_gp
+    gp = fit_structured_gp(600, M, seed=1, use_sparse=True)
+    X0, U, rs = _inputs6(2, 4, M)
+    p = _propagator(_dyn6(False), gp, gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, U, _spread(rs, 2, 14, 1e-2), monkeypatch)
+    _assert_sharp(dev, host, f"14-state FITC M={M}")
+
+
+# ---- edges -----------------------------------------------------------------------------
+@pytest.mark.parametrize("B,N,s0", [(2, 0, "batch"), (3, 1, "batch"), (1, 5, "none"), (3, 3, "shared")],
+                         ids=["N0", "N1", "B1-sigma0-none", "sigma0-broadcast"])
+def test_edges_3dof(gpu_ctx, monkeypatch, gp3_exact, f1, B, N, s0):
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    X0, U, rs = _inputs3(f1, B, N, 31 + N)
+    S0 = {"none": None, "batch": _spread(rs, B, 7, 1e-2), "shared": _spread(rs, 1, 7, 1e-2)[0]}[s0]
+    p = _propagator(create_normalized_rocket(), gp3_exact, gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    want = np.eye(7) * 1e-6 if S0 is None else S0
+    np.testing.assert_array_equal(dev[1][:, 0], np.broadcast_to(want, (B, 7, 7)))
+    _assert_sharp(dev, host, f"3-DoF B={B} N={N} Sigma_0={s0}")
+
+
+@pytest.mark.parametrize("B,N,s0", [(2, 0, "batch"), (1, 1, "none"), (2, 2, "shared")],
+                         ids=["N0", "B1-N1-sigma0-none", "sigma0-broadcast"])
+def test_edges_6dof(gpu_ctx, monkeypatch, gps6, B, N, s0):
+    _ctx_default(gpu_ctx)
+    X0, U, rs = _inputs6(B, N, 41 + N)
+    S0 = {"none": None, "batch": _spread(rs, B, 14, 1e-2), "shared": _spread(rs, 1, 14, 1e-2)[0]}[s0]
+    p = _propagator(_dyn6(False), gps6[True], gpu_ctx, SHARP)
+    dev, host = _device_and_host(p, X0, U, S0, monkeypatch)
+    want = np.eye(14) * 1e-6 if S0 is None else S0
+    np.testing.assert_array_equal(dev[1][:, 0], np.broadcast_to(want, (B, 14, 14)))
+    _assert_sharp(dev, host, f"14-state B={B} N={N} Sigma_0={s0}")
+
+
+def _indefinite(S0):
+    S = S0.copy()
+    S[1] = np.diag(np.r_[-1e-4, np.full(S.shape[-1] - 1, 1e-4)])
+    return S
+
+
+def test_indefinite_sigma0_3dof(gpu_ctx, gp3_exact, f1):
+    """An indefinite Sigma_0 for one of three trajectories: an error return, not a fault.
+    info names the step, that trajectory's later rows are NaN, the other two are what they
+    are without it; the surface and the host loop raise LinAlgError."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd import _lib
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    dyn = create_normalized_rocket()
+    X0, U, rs = _inputs3(f1, 3, 4, 51)
+    S0 = _indefinite(_spread(rs, 3, 7, 1e-2))
+    h = gp3_exact.gp.device_handle
+    args = dict(dt=0.1, alpha=float(dyn.params.alpha), g=np.asarray(dyn.params.g_vec, float), ut=SHARP)
+    m, c, info = _lib.uprop3_unscented(gpu_ctx, h, True, X0, U, S0, **args)
+    assert info.tolist() == [0, 1, 0]
+    np.testing.assert_array_equal(m[1, 0], X0[1]); np.testing.assert_array_equal(c[1, 0], S0[1])
+    assert np.all(np.isnan(m[1, 1:])) and np.all(np.isnan(c[1, 1:]))
+    keep = [0, 2]
+    m2, c2, info2 = _lib.uprop3_unscented(gpu_ctx, h, True, X0[keep], U[keep], S0[keep], **args)
+    assert info2.tolist() == [0, 0]
+    np.testing.assert_array_equal(m[keep], m2); np.testing.assert_array_equal(c[keep], c2)
+    p = _propagator(dyn, gp3_exact, gpu_ctx, SHARP)
+    with pytest.raises(np.linalg.LinAlgError, match="trajectory 1, step 0"):
+        p.propagate_unscented_batch(X0, U, S0, 0.1)
+    p.use_device = False
+    with pytest.raises(np.linalg.LinAlgError):
+        p.propagate_unscented_batch(X0, U, S0, 0.1)
+    mh, ch = p.propagate_unscented_batch(X0[keep], U[keep], S0[keep], 0.1)
+    _assert_sharp((m2, c2), (mh, ch), "3-DoF, the two definite trajectories")
+
+
+def test_indefinite_sigma0_6dof(gpu_ctx, gps6):
+    _ctx_default(gpu_ctx)
+    X0, U, rs = _inputs6(3, 3, 52)
+    S0 = _indefinite(_spread(rs, 3, 14, 1e-2))
+    p = _propagator(_dyn6(False), gps6[True], gpu_ctx, SHARP)
+    m, c, info = p._device_unscented(X0, U, S0, 0.1)
+    assert info.tolist() == [0, 1, 0]
+    assert np.all(np.isnan(m[1, 1:])) and np.all(np.isnan(c[1, 1:]))
+    assert np.all(np.isfinite(m[[0, 2]])) and np.all(np.isfinite(c[[0, 2]]))
+    with pytest.raises(np.linalg.LinAlgError, match="trajectory 1, step 0"):
+        p.propagate_unscented_batch(X0, U, S0, 0.1)
+
+
+# ---- dispatch --------------------------------------------------------------------------
+def test_propagate_dispatch(gpu_ctx, monkeypatch, gp3_exact, f1):
+    """method="unscented" makes exactly one device call and returns a PropagatedUncertainty;
+    "linear" and "monte_carlo" make none of the new calls."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd import _lib
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.mpc import PropagatedUncertainty, UncertaintyPropagator
+    calls = []
+    real = _lib.uprop3_unscented
+    monkeypatch.setattr(_lib, "uprop3_unscented", lambda *a, **k: calls.append(1) or real(*a, **k))
+    monkeypatch.setattr(_lib, "uprop6_unscented", lambda *a, **k: pytest.fail("the 14-state call on a 3-DoF model"))
+    X0, U, _ = _inputs3(f1, 1, 6, 61)
+    dyn = create_normalized_rocket()
+    r = UncertaintyPropagator(dyn, gp3_exact, method="unscented", ctx=gpu_ctx).propagate(X0[0], U[0], None, 0.1)
+    assert len(calls) == 1 and isinstance(r, PropagatedUncertainty)
+    assert r.means.shape == (7, 7) and r.covariances.shape == (7, 7, 7) and np.all(np.isfinite(r.covariances))
+    np.random.seed(0)
+    for method in ("linear", "monte_carlo"):
+        UncertaintyPropagator(dyn, gp3_exact, method=method, ctx=gpu_ctx).propagate(X0[0], U[0], None, 0.1)
+    assert len(calls) == 1
