@@ -179,6 +179,8 @@ _sig("gpmpc_fleet_mc_read_log", _c, _vp, _c, _c, _dp, _dp, _ip)
 _sig("gpmpc_fleet_mc_detach", _c, _vp)
 _sig("gpmpc_nn_dist", _c, _vp, _dp, _c, _dp, _c, _c, _dp)
 _sig("gpmpc_select_diverse", _c, _vp, _dp, _c, _c, _dp, _c, ctypes.c_double, _c, _ip, _dp)
+_sig("gpmpc_kmeans_lloyd", _c, _vp, _dp, _c, _c, _dp, _c, _c, _dp, _ip, _ip, _dp, _ip)
+_sig("gpmpc_kmeans_tau", ctypes.c_double, _c)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -220,7 +222,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_fleet_mc_attach", "gpmpc_fleet_mc_read_log", "gpmpc_fleet_mc_detach",
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
-            "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented"]
+            "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
+            "gpmpc_kmeans_tau"]
 
 
 class HIPError(RuntimeError):
@@ -810,6 +813,37 @@ def select_diverse(ctx, X, scores, n_select, diversity_weight=0.5, path=0):
     _chk(_L.gpmpc_select_diverse(ctx.h, _d(X), n, d, _d(scores), n_select, float(diversity_weight), int(path),
                                  _i(idx), _d(comb)), "select_diverse")
     return idx.astype(np.int64), comb
+
+
+# ---- k-means for the inducing points (csrc/kmeans.hip) ---------------------------
+# the kernels' shape constants (csrc/kmeans.hip; tests/test_kmeans_host.py keeps them equal)
+KMEANS_TILE = 128      # centres per LDS tile of the assign kernel
+KMEANS_OBS = 64        # observations per workgroup of the assign kernel
+KMEANS_WAVES = 8       # its waves: each scans every eighth centre of a tile
+KMEANS_MAXD = 32
+
+
+def kmeans_tau(d):
+    """gpmpc_kmeans_tau: the margin at or below which a nearest-centre decision is unsafe."""
+    return float(_L.gpmpc_kmeans_tau(int(d)))
+
+
+def kmeans_lloyd(ctx, X, C0, iters=10):
+    """gpmpc_kmeans_lloyd: ``iters`` Lloyd iterations over X (n, d) from the code book C0
+    (k, d) -> (C (k, d), labels (n,) int64 of the last assignment, empties (iters,) centres
+    without observations per iteration, min_margin, unsafe).  With unsafe == 0, C and labels
+    are the bits of ``scipy.cluster.vq.kmeans2(X, C0, iter=iters, minit="matrix")``."""
+    X = f64(np.atleast_2d(X)); C0 = f64(np.atleast_2d(C0))
+    n, d = X.shape; k = C0.shape[0]
+    if C0.shape[1] != d:
+        raise ValueError(f"kmeans_lloyd: X has {d} features, C0 {C0.shape[1]}")
+    _finite(X, "kmeans_lloyd: X"); _finite(C0, "kmeans_lloyd: C0")
+    iters = int(iters)
+    C = np.empty((k, d)); labels = np.zeros(n, np.int32); empties = np.zeros(max(iters, 0), np.int32)
+    margin = np.zeros(1); unsafe = np.zeros(1, np.int32)
+    _chk(_L.gpmpc_kmeans_lloyd(ctx.h, _d(X), n, d, _d(C0), k, iters, _d(C), _i(labels), _i(empties), _d(margin),
+                               _i(unsafe)), "kmeans_lloyd")
+    return C, labels.astype(np.int64), empties.astype(np.int64), float(margin[0]), int(unsafe[0])
 
 
 # ---- diagnostic: the internal GEMM launchers (gpmpc_gemm_diag) -----------------

@@ -4,9 +4,10 @@ SparseGP.fit -> gpmpc_fitc_fit: K_uu + jitter I -> L_uu, A = L_uu^-1 K_uf,
 Lambda = max(sigma2 - colsum(A^2) + sigma_n^2, 1e-10), B = I + A Lambda^-1 A^T
 -> L_B, alpha, FITC LML (sparse_gp.py:150-219); predict -> gpmpc_fitc_predict
 (mean as written; variance sigma2 - |v|^2 + |w|^2, sparse_gp.py:
-255-305).  Inducing points are chosen on the host exactly like the reference
-(scipy kmeans2 on the global RNG, random-subset fallback, sparse_gp.py:122-148);
-MultiOutputSparseGP shares them and fits all outputs with one device call.
+255-305).  Inducing points are the reference's (scipy kmeans2 on the global RNG,
+random-subset fallback, sparse_gp.py:122-148): the draw is scipy's, Lloyd's iteration runs
+on the device and gives kmeans2's bits (gp/kmeans.py; GPMPC_KMEANS=host keeps
+it all in scipy); MultiOutputSparseGP shares them and fits all outputs with one device call.
 method="vfe" -> gpmpc_vfe_fit: B = K_uu + K_uf K_fu / sigma_n^2 + jitter I -> L_B,
 alpha = B^-1 K_uf y / sigma_n^2, the VFE bound (sparse_gp.py:221-249); the
 reference predicts both methods with one body, and so does the device handle.
@@ -19,6 +20,7 @@ import numpy as np
 from scipy.cluster.vq import kmeans2
 
 from .. import _lib
+from . import kmeans as _kmeans
 from .exact_gp import GPPrediction, _spec
 from .kernels import Kernel, SquaredExponentialARD
 
@@ -65,6 +67,8 @@ class SparseGP:
         n = X.shape[0]
         if n <= self.n_inducing:
             return X.copy()
+        if _kmeans.mode() == "device" and _kmeans.device_eligible(X, self.n_inducing):
+            return _kmeans.kmeans2_points(X, self.n_inducing)[0]
         try:
             Z, _ = kmeans2(X, self.n_inducing, minit="points")
         except Exception:
@@ -120,6 +124,15 @@ class SparseGP:
         X_all = np.vstack([self.X_train, np.atleast_2d(X_new)])
         y_all = np.concatenate([y_den, np.atleast_1d(y_new)])
         return self.fit(X_all, y_all)
+
+    def optimize_inducing_locations(self, n_iterations: int = 100, learning_rate: float = 0.01,
+                                    verbose: bool = False) -> dict:
+        """sparse_gp.py:355-380: redraw Z by k-means on the current data and refit."""
+        if self.X_train is not None:
+            self._Z = self._initialize_inducing_points(self.X_train)
+            y_den = self.y_train * self._y_std + self._y_mean
+            self.fit(self.X_train, y_den)
+        return {"n_iterations": 0, "method": "kmeans"}
 
     def __repr__(self) -> str:
         return f"SparseGP(n_train={self.n_train}, n_inducing={self.n_inducing}, method={self.method})"

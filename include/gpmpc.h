@@ -700,6 +700,24 @@ int gpmpc_nn_dist(gpmpc_ctx *ctx, const double *X, int n, const double *R, int r
 int gpmpc_select_diverse(gpmpc_ctx *ctx, const double *X, int n, int d, const double *scores, int n_select,
                          double diversity_weight, int path, int *idx_out, double *combined_out);
 
+/* ---- k-means for the sparse GP's inducing points ---------------------------
+ * Lloyd's iteration of scipy.cluster.vq.kmeans2 (SparseGP._initialize_inducing_points,
+ * sparse_gp.py:122-148) from the code book C0 (k x d): `iters` times label = index of the
+ * nearest centre (lowest index on equal distances), then every centre = the mean of its
+ * observations, summed in ascending observation order and divided once by the count; a
+ * centre without observations keeps its row.  X n x d, C0 k x d (host,
+ * row-major); C_out k x d the last code book, labels_out n the labels of the last
+ * assignment (from before the last update, as kmeans2 returns them), empty_per_iter
+ * `iters` counts of centres without observations.
+ * min_margin: the smallest (second nearest - nearest squared distance) / (|x|^2 + max_j
+ * |c_j|^2) over every decision of the call; unsafe: the decisions with a margin <=
+ * gpmpc_kmeans_tau(d) = 16 (d + 2) 2^-53, within which the rounding of scipy's distance
+ * formula and of this one may order two centres differently.  With unsafe = 0 the labels
+ * and the code book are kmeans2's bits.  1 <= d <= 32, n, k, iters >= 1 (k > n allowed). */
+int gpmpc_kmeans_lloyd(gpmpc_ctx *ctx, const double *X, int n, int d, const double *C0, int k, int iters,
+                       double *C_out, int *labels_out, int *empty_per_iter, double *min_margin, int *unsafe);
+double gpmpc_kmeans_tau(int d);
+
 #ifdef __cplusplus
 }
 #endif
