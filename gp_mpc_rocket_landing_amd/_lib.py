@@ -20,6 +20,10 @@ REC_LEN = 16
 COMM_ID_BYTES = 128   # GPMPC_COMM_ID_BYTES (sizeof ncclUniqueId)
 # caps of the generic device QP (csrc/qp.h QP_NMAX, QP_MMAX, QP_NNZMAX)
 QP_NMAX, QP_MMAX, QP_NNZMAX = 216, 360, 896
+# ... and of its KKT factor: half-bandwidth, entries per row / column of A (QP_W, QP_RMAX, QP_CMAX)
+QP_WMAX, QP_ROWMAX, QP_COLMAX = 16, 8, 12
+# gpmpc_qp_pattern_info's answer, in order (include/gpmpc.h)
+QP_PATTERN_INFO = ("mode", "w", "nblk", "fac_len", "maxrow", "maxcol", "n_offd", "fits", "is_fleet_pattern")
 
 QP_STATUS = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached",
              -3: "primal infeasible", 3: "primal infeasible inaccurate", -4: "dual infeasible",
@@ -137,6 +141,7 @@ _sig("gpmpc_fitc_get_state", _c, _vp, _vp, _dp)
 _sig("gpmpc_qp_default_settings", None, ctypes.POINTER(QPSettings))
 _sig("gpmpc_qp_solve_batched", _c, _vp, _c, _c, _c, _c, _ip, _ip, _dp, _dp, _dp, _dp, _dp,
      ctypes.POINTER(QPSettings), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp)
+_sig("gpmpc_qp_pattern_info", _c, _c, _c, _ip, _ip, _ip)
 _sig("gpmpc_fleet_default_config", None, ctypes.POINTER(FleetConfig))
 _sig("gpmpc_fleet_create", _c, _vp, _vp, ctypes.POINTER(FleetConfig), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_fleet_create_shard", _c, _vp, _vp, ctypes.POINTER(FleetConfig), _c, _c, ctypes.POINTER(_vp))
@@ -223,7 +228,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
             "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
-            "gpmpc_kmeans_tau"]
+            "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info"]
 
 
 class HIPError(RuntimeError):
@@ -569,6 +574,17 @@ def qp_default_settings(**kw):
     s = QPSettings()
     _L.gpmpc_qp_default_settings(ctypes.byref(s))
     return set_fields(s, kw)
+
+
+def qp_pattern_info(n, m, rowptr, colidx):
+    """gpmpc_qp_pattern_info: which KKT factor path the batched QP takes for the CSR pattern
+    (rowptr, colidx) of an m x n A, as a dict over QP_PATTERN_INFO.  Host only: no context."""
+    rp = np.ascontiguousarray(rowptr, np.int32); ci = np.ascontiguousarray(colidx, np.int32)
+    if rp.size != int(m) + 1 or ci.size < int(rp[-1]):
+        raise ValueError(f"rowptr needs m + 1 = {int(m) + 1} entries and colidx rowptr[m], got {rp.size}, {ci.size}")
+    info = np.zeros(len(QP_PATTERN_INFO), np.int32)
+    _chk(_L.gpmpc_qp_pattern_info(int(n), int(m), _i(rp), _i(ci), _i(info)), "qp_pattern_info")
+    return dict(zip(QP_PATTERN_INFO, (int(v) for v in info)))
 
 
 def rollout6_default_config(**kw):

@@ -7,6 +7,7 @@
 // workgroup; the numeric data of each problem is staged into LDS.
 #include "internal.h"
 #include "qp.h"
+#include "qp_pattern.h"
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -42,139 +43,45 @@ QPSettingsDev to_dev(const gpmpc_qp_settings &s) {
 }
 
 int QPPatternHost::build(int n_, int m_, const int *rowptr, const int *colidx, hipStream_t s) {
-  n = n_;
-  m = m_;
-  nnz = rowptr[m];
-  w = 0;
-  for (int r = 0; r < m; ++r)
-    for (int a = rowptr[r]; a < rowptr[r + 1]; ++a)
-      for (int b = rowptr[r]; b < rowptr[r + 1]; ++b) w = std::max(w, colidx[a] - colidx[b]);
-  const int nb = w + 1;
-  maxrow = 0;
-  for (int r = 0; r < m; ++r) maxrow = std::max(maxrow, rowptr[r + 1] - rowptr[r]);
-  // CSC map
-  std::vector<int> colptr(n + 1, 0), csc2csr(nnz), cscrow(nnz);
-  for (int k = 0; k < nnz; ++k) colptr[colidx[k] + 1]++;
-  for (int j = 0; j < n; ++j) colptr[j + 1] += colptr[j];
-  maxcol = 0;
-  for (int j = 0; j < n; ++j) maxcol = std::max(maxcol, colptr[j + 1] - colptr[j]);
-  std::vector<int> fill(colptr.begin(), colptr.end() - 1);
-  for (int r = 0; r < m; ++r)
-    for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) {
-      const int p = fill[colidx[k]]++;
-      csc2csr[p] = k;
-      cscrow[p] = r;
-    }
-  // Factor layout.  Mode 1 (block tridiagonal, qp_block.h) when every coupled
-  // pair (i >= j) of M = P + A'RA lies in one block of QP_BLK_SZ variables or
-  // in neighbouring blocks with i among the first QP_BLK_CM rows of its block
-  // (the MPC stage structure); otherwise mode 0, the banded LDL^T with column
-  // stride QP_W+1.  Either way every LDS slot gets its list of rho_r A[a] A[b]
-  // terms, generated in (row, a, b) order like the C oracle's factor().
-  constexpr int NB = QP_W + 1, SZ = QP_BLK_SZ, CM = QP_BLK_CM, BS = SZ * SZ + SZ * CM;
-  nblk = (n + SZ - 1) / SZ;
-  bool blk = true;
-  for (int r = 0; r < m && blk; ++r)
-    for (int a = rowptr[r]; a < rowptr[r + 1]; ++a)
-      for (int b = rowptr[r]; b < rowptr[r + 1]; ++b) {
-        const int i = colidx[a], j = colidx[b];
-        if (j > i) continue;
-        const int bi = i / SZ, bj = j / SZ;
-        if (!(bi == bj || (bi == bj + 1 && i - bi * SZ < CM))) blk = false;
-      }
-  if (blk && nblk * BS - SZ * CM > QP_FAC_CAP) blk = false;
-  mode = blk ? 1 : 0;
-  fac_len = blk ? nblk * BS - SZ * CM : n * NB;
-  struct T { int e, r, a, b; };
-  std::vector<T> terms;
-  std::vector<int> facdiag(fac_len, -1);
-  for (int r = 0; r < m; ++r)
-    for (int a = rowptr[r]; a < rowptr[r + 1]; ++a)
-      for (int b = rowptr[r]; b < rowptr[r + 1]; ++b) {
-        const int i = colidx[a], j = colidx[b];
-        if (j > i) continue;
-        if (!blk) {
-          terms.push_back(T{j * NB + (i - j), r, a, b});
-          continue;
-        }
-        const int bi = i / SZ, bj = j / SZ, ri = i - bi * SZ, rj = j - bj * SZ;
-        if (bi == bj) {
-          terms.push_back(T{bi * BS + rj * SZ + ri, r, a, b});
-          if (i != j) terms.push_back(T{bi * BS + ri * SZ + rj, r, a, b});
-        } else {
-          terms.push_back(T{bj * BS + SZ * SZ + rj * CM + ri, r, a, b});
-        }
-      }
-  if (blk) {
-    for (int v = 0; v < nblk * SZ; ++v) {
-      const int k = v / SZ, rv = v - k * SZ;
-      facdiag[k * BS + rv * SZ + rv] = (v < n) ? v : -2;  // identity rows pad the last block
-    }
-  } else {
-    for (int j = 0; j < n; ++j) facdiag[j * NB] = j;
-  }
-  std::stable_sort(terms.begin(), terms.end(), [](const T &x, const T &y) { return x.e < y.e; });
-  std::vector<int> facptr(fac_len + 1, 0), tv(3 * terms.size());
-  for (size_t k = 0; k < terms.size(); ++k) {
-    facptr[terms[k].e + 1]++;
-    tv[3 * k] = terms[k].r;
-    tv[3 * k + 1] = terms[k].a;
-    tv[3 * k + 2] = terms[k].b;
-  }
-  for (int e = 0; e < fac_len; ++e) facptr[e + 1] += facptr[e];
-  // mode 1: the non-diagonal slots that are not plain zeros, one int4 each
-  // (QPPattern::offd), so the fleet's assembly reads one coalesced item per
-  // slot instead of walking facdiag / facptr / terms for every slot
-  std::vector<int> offd;
-  int n_offd = -1;
-  if (blk && fac_len < (1 << 15) && nnz < (1 << 16)) {
-    n_offd = 0;
-    for (int e = 0; e < fac_len && n_offd >= 0; ++e) {
-      if (facdiag[e] >= 0) continue;
-      const int k0 = facptr[e], k1 = facptr[e + 1], one = facdiag[e] == -2;
-      if (k1 == k0 && !one) continue;
-      if (k1 - k0 > 3) { n_offd = -1; break; }
-      int it[4] = {e | (one << 15) | ((k1 - k0) << 16), 0, 0, 0};
-      for (int k = k0; k < k1; ++k) it[1 + k - k0] = tv[3 * k + 1] | (tv[3 * k + 2] << 16);
-      offd.insert(offd.end(), it, it + 4);
-      ++n_offd;
-    }
-  }
-  if (n_offd < 0) offd.clear();
-  // one device block: rowptr | colidx | colptr | csc2csr | cscrow | facptr | facdiag | terms | offd
-  std::vector<int> all;
-  auto app = [&](const int *p, size_t k) { all.insert(all.end(), p, p + k); };
-  const size_t o_rp = 0;
-  app(rowptr, m + 1);
-  const size_t o_ci = all.size();
-  app(colidx, nnz);
-  const size_t o_cp = all.size();
-  app(colptr.data(), n + 1);
-  const size_t o_cm = all.size();
-  app(csc2csr.data(), nnz);
-  const size_t o_cr = all.size();
-  app(cscrow.data(), nnz);
-  const size_t o_bp = all.size();
-  app(facptr.data(), facptr.size());
-  const size_t o_fd = all.size();
-  app(facdiag.data(), facdiag.size());
-  const size_t o_tv = all.size();
-  app(tv.data(), tv.size());
-  while (all.size() % 4) all.push_back(0);  // int4 alignment (the buffer itself is 256-B aligned)
-  const size_t o_od = all.size();
-  app(offd.data(), offd.size());
-  if (buf.alloc(sizeof(int) * all.size()) != hipSuccess) return -1;
-  if (hipMemcpyAsync(buf.p, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice, s) !=
+  const QPPatternPlan pl = qp_pattern_analyze(n_, m_, rowptr, colidx);  // host only (qp_pattern.h)
+  n = pl.n; m = pl.m; nnz = pl.nnz; w = pl.w; maxrow = pl.maxrow; maxcol = pl.maxcol;
+  mode = pl.mode; fac_len = pl.fac_len; nblk = pl.nblk;
+  if (buf.alloc(sizeof(int) * pl.all.size()) != hipSuccess) return -1;
+  if (hipMemcpyAsync(buf.p, pl.all.data(), sizeof(int) * pl.all.size(), hipMemcpyHostToDevice, s) !=
           hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return -1;
   const int *d = buf.as<int>();
   dev.n = n; dev.m = m; dev.nnz = nnz; dev.w = w;
-  dev.rowptr = d + o_rp; dev.colidx = d + o_ci; dev.colptr = d + o_cp; dev.csc2csr = d + o_cm;
-  dev.cscrow = d + o_cr; dev.facptr = d + o_bp; dev.facdiag = d + o_fd; dev.terms = d + o_tv;
-  dev.mode = mode; dev.fac_len = fac_len; dev.nblk = nblk; dev.bsz = SZ; dev.bcm = CM;
-  dev.offd = reinterpret_cast<const int4 *>(d + o_od);
-  dev.n_offd = n_offd;
+  dev.rowptr = d + pl.o_rp; dev.colidx = d + pl.o_ci; dev.colptr = d + pl.o_cp; dev.csc2csr = d + pl.o_cm;
+  dev.cscrow = d + pl.o_cr; dev.facptr = d + pl.o_bp; dev.facdiag = d + pl.o_fd; dev.terms = d + pl.o_tv;
+  dev.mode = mode; dev.fac_len = fac_len; dev.nblk = nblk; dev.bsz = QP_BLK_SZ; dev.bcm = QP_BLK_CM;
+  dev.offd = reinterpret_cast<const int4 *>(d + pl.o_od);
+  dev.n_offd = pl.n_offd;
+  return 0;
+}
+
+// the refusals of a malformed pattern: what qp_pattern_analyze may index with
+static bool qp_pattern_well_formed(int n, int m, const int *rowptr, const int *colidx) {
+  if (n <= 0 || m <= 0 || !rowptr || !colidx || rowptr[0] != 0) return false;
+  for (int r = 0; r < m; ++r)
+    if (rowptr[r + 1] < rowptr[r]) return false;
+  for (int k = 0; k < rowptr[m]; ++k)
+    if (colidx[k] < 0 || colidx[k] >= n) return false;
+  return true;
+}
+
+// which factor path a pattern takes, without a context or a device (include/gpmpc.h)
+extern "C" int gpmpc_qp_pattern_info(int n, int m, const int *rowptr, const int *colidx, int *info) {
+  GPMPC_CHECK_ARG(info && qp_pattern_well_formed(n, m, rowptr, colidx));
+  const QPPatternPlan pl = qp_pattern_analyze(n, m, rowptr, colidx);
+  QPPatternHost h;
+  h.n = pl.n; h.m = pl.m; h.nnz = pl.nnz; h.w = pl.w; h.maxrow = pl.maxrow; h.maxcol = pl.maxcol;
+  h.mode = pl.mode; h.fac_len = pl.fac_len; h.nblk = pl.nblk;
+  const int out[GPMPC_QP_PATTERN_INFO_INTS] = {pl.mode, pl.w, pl.nblk, pl.fac_len, pl.maxrow, pl.maxcol,
+                                               pl.n_offd, h.fits() ? 1 : 0,
+                                               qp_is_fleet_pattern(n, m, rowptr, colidx) ? 1 : 0};
+  std::copy(out, out + GPMPC_QP_PATTERN_INFO_INTS, info);
   return 0;
 }
 
@@ -303,9 +210,9 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
     return -1;
   }
   if (!pat->fits()) {
-    gpmpc_set_error("qp: pattern outside the compiled caps (n %d<=256, m %d<=512, half-bandwidth "
-                    "%d<=%d, row nnz %d<=%d, col nnz %d<=%d)", pat->n, pat->m, pat->w, QP_W,
-                    pat->maxrow, QP_RMAX, pat->maxcol, QP_CMAX);
+    gpmpc_set_error("qp: pattern outside the compiled caps (n %d<=%d, m %d<=%d, half-bandwidth "
+                    "%d<=%d, row nnz %d<=%d, col nnz %d<=%d)", pat->n, QP_NMAX, pat->m, QP_MMAX, pat->w,
+                    QP_W, pat->maxrow, QP_RMAX, pat->maxcol, QP_CMAX);
     return -2;
   }
   // The fleet's solver (fleet_qp.h, registers + twisted KKT solve) for its own pattern -- the
@@ -349,6 +256,13 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
                                 dit, dst, dob, dts.as<unsigned long long>()));
   }
   GPMPC_HIP(sg.download());
+  // a failed factorisation (-100) returns before the kernels write x and y: without this the
+  // caller would read whatever the staging buffer held, e.g. an earlier solve's solution
+  for (int b = 0; b < batch; ++b)
+    if (status[b] == -100) {
+      std::fill(x + (size_t)b * n, x + (size_t)(b + 1) * n, nan(""));
+      std::fill(y + (size_t)b * m, y + (size_t)(b + 1) * m, nan(""));
+    }
   if (stamp) {
     unsigned long long h[16];
     GPMPC_HIP(hipMemcpy(h, dts.p, sizeof(h), hipMemcpyDeviceToHost));

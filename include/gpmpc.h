@@ -322,10 +322,23 @@ int gpmpc_fitc_destroy(gpmpc_fitc *gp);
  * block-tridiagonally (the MPC stage structure: blocks of 10 variables
  * coupled through their first 7, n <= 216) or, for any other pattern, as a
  * banded LDL^T with half-bandwidth <= 16.  Caps: n <= 216, m <= 360,
- * nnz <= 736, <= 8 entries per row and <= 12 per column of A.
+ * nnz <= 896, <= 8 entries per row and <= 12 per column of A
+ * (GPMPC_QP_NMAX / _MMAX / _NNZMAX / _WMAX / _ROWMAX / _COLMAX below); a
+ * pattern outside them is refused with -2 and nothing is written.
  * State carried between solves (OSQP keeps it in its workspace):
- *   rho (batch), y_scaled (batch x m).  x_ws: warm-start primal (unscaled).
- * Outputs: x (batch x n), y (batch x m) unscaled, iters, status, obj. */
+ *   rho (batch), y_scaled (batch x m).  x_ws: warm-start primal (unscaled),
+ *   NULL for zeros.
+ * Outputs: x (batch x n), y (batch x m) unscaled, iters, status, obj.  A
+ * status without a solution (not 1, 2 or -2) has x, y and obj NaN.  Status
+ * -100, a reduced KKT matrix that is not positive definite (a negative
+ * Pdiag entry), is one of them: iters 0, x, y and obj NaN, and that
+ * problem's rho and y_scaled are left as they were passed in. */
+#define GPMPC_QP_NMAX 216
+#define GPMPC_QP_MMAX 360
+#define GPMPC_QP_NNZMAX 896
+#define GPMPC_QP_WMAX 16
+#define GPMPC_QP_ROWMAX 8
+#define GPMPC_QP_COLMAX 12
 typedef struct {
   double rho, sigma, alpha;
   double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
@@ -340,6 +353,16 @@ int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, int nnz, con
                            const gpmpc_qp_settings *s, const double *x_ws, double *rho,
                            double *y_scaled, double *x, double *y, int *iters, int *status,
                            double *obj);
+/* Which KKT factor path gpmpc_qp_solve_batched takes for a pattern; needs no context and
+ * no device.  info (GPMPC_QP_PATTERN_INFO_INTS ints): mode (0 banded LDL^T, 1 block
+ * tridiagonal), half-bandwidth w, nblk (blocks of 10 variables), fac_len (factor slots),
+ * maxrow, maxcol (most entries in a row / column of A), n_offd (mode 1: the slots of the
+ * fleet's coalesced assembly list, -1 when the pattern has none), fits (1: within the caps,
+ * 0: the solve refuses it with -2), is_fleet_pattern (1: the 3-DoF MPC at N = 20, which the
+ * fleet's solver takes).  Returns 0, or -2 for a malformed pattern (n or m <= 0, rowptr not
+ * non-decreasing from 0, a column outside [0, n)). */
+#define GPMPC_QP_PATTERN_INFO_INTS 9
+int gpmpc_qp_pattern_info(int n, int m, const int *rowptr, const int *colidx, int *info);
 
 /* ---- the control step: a fleet of closed-loop 3-DoF GP-MPC landings -------
  * One "step" = for every landing: GP posterior (mean + variance) at the N
