@@ -163,6 +163,10 @@ _sig("gpmpc_uprop3_unscented", _c, _vp, _vp, _c, _c, _c, ctypes.c_double, ctypes
      _vp, ctypes.c_double, _dp, _dp, _ip)
 _sig("gpmpc_uprop6_unscented", _c, _vp, _vp, _vp, _c, _dp, _dp, _c, _c, ctypes.c_double, _dp, _dp, _vp,
      ctypes.c_double, _dp, _dp, _ip)
+_sig("gpmpc_uprop3_mc", _c, _vp, _vp, _c, _c, _c, _c, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _vp,
+     ctypes.c_double, _dp, _dp, _dp, _dp, _vp)
+_sig("gpmpc_uprop6_mc", _c, _vp, _vp, _vp, _c, _dp, _c, _c, _c, ctypes.c_double, _dp, _dp, _vp,
+     ctypes.c_double, _dp, _dp, _dp, _dp, _vp)
 _sig("gpmpc_fleet_read", _c, _vp, _dp, _dp)
 _sig("gpmpc_gram_grad", _c, _vp, _c, _dp, _c, _dp, _c, _c, _dp, ctypes.c_double, _dp, _dp)
 _sig("gpmpc_fleet_get_state", _c, _vp, _dp, _dp, _dp, _dp)
@@ -228,7 +232,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
             "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
-            "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info"]
+            "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc"]
 
 
 class HIPError(RuntimeError):
@@ -765,6 +769,59 @@ def uprop6_unscented(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, ut=(1e-
                                    float(dt), _d(X0), _d(U), s0, float(s0_diag), _d(means), _d(covs), _i(info)),
          "uprop6_unscented")
     return means, covs, info
+
+
+def _mc_buffers(what, nx, groups, X0, U, S0, particles0, normals, return_particles):
+    X0 = f64(np.atleast_2d(X0)); U = f64(U); particles0 = f64(particles0); normals = f64(normals)
+    if U.ndim != 3 or particles0.ndim != 3:
+        raise ValueError(f"{what}: shapes U {U.shape}, particles0 {particles0.shape}")
+    B, N, S = U.shape[0], U.shape[1], particles0.shape[1]
+    if X0.shape != (B, nx) or U.shape != (B, N, 3):
+        raise ValueError(f"{what}: shapes X0 {X0.shape}, U {U.shape}")
+    if particles0.shape != (B, S, nx):
+        raise ValueError(f"{what}: particles0 shape {particles0.shape}, expected {(B, S, nx)}")
+    if normals.shape != (B, N, S, groups, 3):
+        raise ValueError(f"{what}: normals shape {normals.shape}, expected {(B, N, S, groups, 3)}")
+    s0 = None
+    if S0 is not None:
+        S0 = f64(S0)
+        if S0.shape != (B, nx, nx):
+            raise ValueError(f"{what}: S0 shape {S0.shape}")
+        s0 = S0.ctypes.data_as(_vp)
+    paths = np.empty((B, N + 1, S, nx)) if return_particles else None
+    pp = None if paths is None else paths.ctypes.data_as(_vp)
+    return X0, U, S0, s0, particles0, normals, np.empty((B, N + 1, nx)), np.empty((B, N + 1, nx, nx)), paths, pp
+
+
+def uprop3_mc(ctx, gp, exact, X0, U, S0, particles0, normals, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0),
+              return_particles=False, s0_diag=1e-6):
+    """gpmpc_uprop3_mc: the 3-DoF Monte-Carlo uncertainty propagation of B trajectories on the
+    device.  gp, exact as uprop3_unscented; the draws are the caller's: particles0 (B, S, 7)
+    and the standard normals (B, N, S, 1, 3); X0 (B, 7), U (B, N, 3), S0 None or (B, 7, 7) ->
+    means (B, N+1, 7), covariances (B, N+1, 7, 7), and the particles (B, N+1, S, 7) or None."""
+    X0, U, S0, s0, particles0, normals, means, covs, paths, pp = _mc_buffers(
+        "uprop3_mc", 7, 1, X0, U, S0, particles0, normals, return_particles)
+    g3 = f64(np.asarray(g, float).reshape(3))
+    _chk(_L.gpmpc_uprop3_mc(ctx.h, gp.h, int(bool(exact)), U.shape[0], U.shape[1], particles0.shape[1], float(dt),
+                            float(alpha), _d(g3), _d(X0), _d(U), s0, float(s0_diag), _d(particles0), _d(normals),
+                            _d(means), _d(covs), pp), "uprop3_mc")
+    return means, covs, paths
+
+
+def uprop6_mc(ctx, hv, hw, exact, rocket, X0, U, S0, particles0, normals, dt=0.1, return_particles=False,
+              s0_diag=1e-6):
+    """gpmpc_uprop6_mc: the 14-state Monte-Carlo uncertainty propagation of B trajectories on
+    the device.  hv, hw, exact, rocket as uprop6_linear; particles0 (B, S, 14), normals
+    (B, N, S, 2, 3) (per particle the d_v normals, then the d_omega ones); X0 (B, 14), U
+    (B, N, 3), S0 None or (B, 14, 14) -> means (B, N+1, 14), covariances (B, N+1, 14, 14), and
+    the particles (B, N+1, S, 14) or None."""
+    X0, U, S0, s0, particles0, normals, means, covs, paths, pp = _mc_buffers(
+        "uprop6_mc", 14, 2, X0, U, S0, particles0, normals, return_particles)
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    _chk(_L.gpmpc_uprop6_mc(ctx.h, hv.h, hw.h, int(bool(exact)), _d(rk), U.shape[0], U.shape[1],
+                            particles0.shape[1], float(dt), _d(X0), _d(U), s0, float(s0_diag), _d(particles0),
+                            _d(normals), _d(means), _d(covs), pp), "uprop6_mc")
+    return means, covs, paths
 
 
 def cov_propagate(ctx, A, q, S0=None, s0_diag=1e-6):

@@ -53,6 +53,10 @@ struct R6Rocket {
   int full;
 };
 
+// R6Rocket from the 17 doubles of gpmpc_uprop6_linear's packing (uprop_ut.hip); what: the
+// caller's name in the error message.  0, or -2 with the error set.
+int ut_rocket(const double *rocket, R6Rocket &rk, const char *what);
+
 __device__ __forceinline__ void r6_mat3(const double *M, const double *v, double *o) {
   for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * v[0] + M[3 * i + 1] * v[1]) + M[3 * i + 2] * v[2];
 }

@@ -454,8 +454,9 @@ __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
 
 // R6Rocket from the packing of gpmpc_uprop6_linear: J_B (9, row-major), r_T_B (3), g_I (3),
 // alpha, g0.  A diagonal tensor runs as its diagonal, any other as J and J^-1 (adjugate /
-// determinant, the expressions of the rollout's own set-up).  0, or -2 with the error set.
-static int ut_rocket(const double *rocket, R6Rocket &rk) {
+// determinant, the expressions of the rollout's own set-up).  0, or -2 with the error set
+// (what: the caller's name in the message).  Shared with uprop_mc.hip (fleet6.h).
+int ut_rocket(const double *rocket, R6Rocket &rk, const char *what) {
   const double *Jf = rocket;
   bool joff = false;
   for (int i = 0; i < 9; ++i) joff = joff || (i % 4 != 0 && Jf[i] != 0.0);
@@ -466,7 +467,7 @@ static int ut_rocket(const double *rocket, R6Rocket &rk) {
   if (!joff) {
     for (int i = 0; i < 3; ++i)
       if (!(rk.J[i] > 0.0)) {
-        gpmpc_set_error("uprop6_unscented: the rocket's J_B diagonal must be positive");
+        gpmpc_set_error("%s: the rocket's J_B diagonal must be positive", what);
         return -2;
       }
     return 0;
@@ -481,7 +482,7 @@ static int ut_rocket(const double *rocket, R6Rocket &rk) {
     scale = std::max(scale, std::fabs(Jf[i]));
   }
   if (!fin || !(std::fabs(det) > 1e-14 * scale * scale * scale)) {
-    gpmpc_set_error("uprop6_unscented: the rocket's J_B must be finite and invertible");
+    gpmpc_set_error("%s: the rocket's J_B must be finite and invertible", what);
     return -2;
   }
   const double adj[9] = {c00, Jf[2] * Jf[7] - Jf[1] * Jf[8], Jf[1] * Jf[5] - Jf[2] * Jf[4],
@@ -571,7 +572,7 @@ extern "C" int gpmpc_uprop6_unscented(gpmpc_ctx *ctx, void *gp_v, void *gp_w, in
   a.W2v = exact ? nullptr : fitc_W2((gpmpc_fitc *)gp_v);
   a.W2w = exact ? nullptr : fitc_W2((gpmpc_fitc *)gp_w);
   // rocket: J_B (9, row-major), r_T_B (3), g_I (3), alpha, g0 (gpmpc_uprop6_linear's packing)
-  if (ut_rocket(rocket, a.rk)) return -2;
+  if (ut_rocket(rocket, a.rk, "uprop6_unscented")) return -2;
   ut_weights(ut, 14, a);
   a.N = N;
   a.dt = dt;

@@ -17,8 +17,15 @@ The unscented method runs its whole recursion -- Cholesky factor, sigma points,
 model step, GP means and the variance at the centre -- in one device call for a
 batch of trajectories (``propagate_unscented_batch``; ``gpmpc_uprop3_unscented`` /
 ``gpmpc_uprop6_unscented``, csrc/uprop_ut.hip) where the linear device paths'
-gates accept, and the per-step host loop elsewhere.  Monte-Carlo propagation is
-host numpy (it consumes the global RNG in the reference's draw order).
+gates accept, and the per-step host loop elsewhere.
+
+The Monte-Carlo method draws on the host -- numpy's global RNG in the reference's
+order, so a seed means what it means there -- and under the same gates runs the
+particles of a batch of trajectories in one device call
+(``propagate_monte_carlo_batch``; ``gpmpc_uprop3_mc`` / ``gpmpc_uprop6_mc``,
+csrc/uprop_mc.hip): per horizon step one GP posterior at all B * n_samples
+particles, the per-particle plant step with the sampled residual, and the sample
+statistics at the end.  Elsewhere the per-step host loop consumes the same draws.
 
 Both model shapes work: the reference's 14-state 6-DoF model with a 4-tuple GP
 (StructuredRocketGP: residuals on v-dot 4:7 and omega-dot 11:14), and the
@@ -341,31 +348,114 @@ class UncertaintyPropagator:
 
     # ------------------------------------------------------------- Monte Carlo
     def _propagate_monte_carlo(self, x0, U, Sigma_0, dt, n_samples: int = 100) -> PropagatedUncertainty:
-        """uncertainty_prop.py:266-315.  Draws from numpy's global RNG in the
-        reference's order (per particle: 3 normals for d_v, then 3 for d_omega;
-        the 3-DoF model draws only the d_v ones); the particles' GP evaluations
-        are one batch per step."""
+        """uncertainty_prop.py:266-315 for one trajectory (a batch of one)."""
+        S0 = None if Sigma_0 is None else np.asarray(Sigma_0, float)[None]
         U = np.atleast_2d(np.asarray(U, float))
+        means, covs = self.propagate_monte_carlo_batch(np.asarray(x0, float)[None], U[None], S0, dt, n_samples)
+        return PropagatedUncertainty(means=means[0], covariances=covs[0])
+
+    def _monte_carlo_draw(self, X0, S0, N, n_samples):
+        """The draws of B trajectories from numpy's global RNG, in the order of a caller who
+        loops over them with the reference: per trajectory the particles of step 0
+        (multivariate_normal), then per step and particle 3 normals for d_v and, for the
+        14-state model, 3 for d_omega.  -> particles0 (B, S, n), z (B, N, S, G, 3)."""
+        B, n = X0.shape
+        G = 2 if n == 14 else 1
+        particles0 = np.empty((B, n_samples, n)); z = np.empty((B, N, n_samples, G, 3))
+        for b in range(B):
+            particles0[b] = np.random.multivariate_normal(X0[b], np.eye(n) * 1e-6 if S0 is None else S0[b], n_samples)
+            for k in range(N):
+                z[b, k] = np.random.randn(n_samples, G, 3)
+        return particles0, z
+
+    def _device_monte_carlo(self, X0, U, S0, dt, particles0, z, return_particles):
+        """The whole Monte-Carlo propagation of every trajectory in one device call
+        (gpmpc_uprop3_mc / gpmpc_uprop6_mc, csrc/uprop_mc.hip) where the gates of the
+        unscented device path accept.  (means, covs, particles | None), or None: the host loop."""
+        try:
+            gate = self._gate_3dof(sparse_ok=True)
+            if gate is not None:
+                p = self.dynamics.params
+                return _lib.uprop3_mc(self.ctx, gate[0], gate[1], X0, U, S0, particles0, z, dt, float(p.alpha),
+                                      np.asarray(p.g_vec, float), return_particles)
+            gate = self._gate_6dof()
+            if gate is not None:
+                hv, hw, exact, rocket = gate
+                return _lib.uprop6_mc(self.ctx, hv, hw, exact, rocket, X0, U, S0, particles0, z, dt,
+                                      return_particles)
+        except _lib.HIPError:
+            pass   # (a composite-kernel GP: the host loop)
+        return None
+
+    def propagate_monte_carlo_batch(self, X0, U, Sigma_0=None, dt: float = 0.1, n_samples: int = 100,
+                                    return_particles: bool = False):
+        """Monte-Carlo propagation of B trajectories at once.
+
+        X0 (B, n_x), U (B, N, n_u), Sigma_0 None (the reference's 1e-6 I), (n_x, n_x) or
+        (B, n_x, n_x) -> means (B, N+1, n_x), covariances (B, N+1, n_x, n_x), and with
+        return_particles the particles (B, N+1, n_samples, n_x).  The draws come from numpy's
+        global RNG exactly as for a caller looping over the trajectories with the reference
+        (_monte_carlo_draw), on either path.  One device call where _device_monte_carlo
+        accepts, else the host loop once per trajectory over the same draws."""
+        X0 = np.atleast_2d(np.asarray(X0, float)); U = np.asarray(U, float)
+        if U.ndim == 2:
+            U = U[None]
+        B, N = U.shape[0], U.shape[1]
+        nx = self.n_x
+        if X0.shape != (B, nx):
+            raise ValueError(f"X0 shape {X0.shape}, expected {(B, nx)}")
+        if n_samples < 2:
+            raise ValueError(f"n_samples {n_samples}: the sample covariance needs at least 2")
+        S0 = None
+        if Sigma_0 is not None:
+            S0 = np.asarray(Sigma_0, float)
+            if S0.shape not in ((nx, nx), (B, nx, nx)):
+                raise ValueError(f"Sigma_0 shape {S0.shape}, expected {(nx, nx)} or {(B, nx, nx)}")
+            S0 = np.broadcast_to(S0, (B, nx, nx))
+        particles0, z = self._monte_carlo_draw(X0, S0, N, n_samples)
+        dev = self._device_monte_carlo(X0, U, S0, dt, particles0, z, return_particles)
+        if dev is None:
+            means = np.zeros((B, N + 1, nx)); covs = np.zeros((B, N + 1, nx, nx))
+            paths = np.zeros((B, N + 1, n_samples, nx)) if return_particles else None
+            for b in range(B):
+                r = self._monte_carlo_host(X0[b], U[b], None if S0 is None else S0[b], dt, particles0[b], z[b],
+                                           return_particles)
+                means[b], covs[b] = r[0], r[1]
+                if return_particles:
+                    paths[b] = r[2]
+            dev = (means, covs, paths)
+        return dev if return_particles else dev[:2]
+
+    def _monte_carlo_host(self, x0, U, Sigma_0, dt, particles0, z, return_particles=False):
+        """uncertainty_prop.py:266-315 over given draws: particles0 (S, n), z (N, S, G, 3);
+        the particles' GP evaluations are one batch per step.  -> (means, covs, and the
+        particles (N+1, S, n) or None)."""
+        U = np.atleast_2d(np.asarray(U, float)).reshape(-1, 3)
         N, n = len(U), self.n_x
+        n_samples = len(particles0)
         if Sigma_0 is None:
             Sigma_0 = np.eye(n) * 1e-6
         rv, rw = self._rows()
-        particles = np.random.multivariate_normal(x0, Sigma_0, n_samples)
+        particles = particles0
         means = np.zeros((N + 1, n)); covs = np.zeros((N + 1, n, n))
+        paths = np.zeros((N + 1, n_samples, n)) if return_particles else None
         means[0] = x0; covs[0] = Sigma_0
+        if return_particles:
+            paths[0] = particles0
         for k in range(N):
             u_k = U[k]
             d_v, d_w, var_v, var_w = _gp_batch(self.gp, particles, np.broadcast_to(u_k, (n_samples, 3)))
             nxt = np.array([self.dynamics.step(particles[i], u_k, dt) for i in range(n_samples)])
-            z = np.random.randn(n_samples, 2 if rw is not None else 1, 3)
-            nxt[:, rv] += (d_v + np.sqrt(var_v) * z[:, 0]) * dt
+            nxt[:, rv] += (d_v + np.sqrt(var_v) * z[k][:, 0]) * dt
             if rw is not None:
-                nxt[:, rw] += (d_w + np.sqrt(var_w) * z[:, 1]) * dt
+                nxt[:, rw] += (d_w + np.sqrt(var_w) * z[k][:, 1]) * dt
             means[k + 1] = np.mean(nxt, axis=0)
             diff = nxt - means[k + 1]
             covs[k + 1] = (diff.T @ diff) / (n_samples - 1)
+            if return_particles:
+                paths[k + 1] = nxt
             particles = nxt
-        return PropagatedUncertainty(means=means, covariances=covs)
+        return means, covs, paths
 
 
 class ConstraintTightening:

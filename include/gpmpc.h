@@ -559,6 +559,33 @@ int gpmpc_uprop3_unscented(gpmpc_ctx *ctx, void *gp, int exact, int batch, int N
 int gpmpc_uprop6_unscented(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact, const double *rocket,
                            const double *ut, int batch, int N, double dt, const double *x0, const double *U,
                            const double *S0, double s0_diag, double *means, double *covs, int *info);
+/* UncertaintyPropagator._propagate_monte_carlo (uncertainty_prop.py:266-315) of the 3-DoF
+ * model on the device, for batch trajectories of n_samples (>= 2) particles in one call.  The
+ * draws are the caller's (numpy's global RNG in the reference's order): particles0 (batch x
+ * n_samples x 7), the particles at step 0, and normals (batch x N x n_samples x 1 x 3), the
+ * standard normals of every step.  Per step: one posterior at all batch * n_samples particles,
+ * then per particle the explicit-Euler step plus (d + sqrt(var) z) dt on the velocity rows
+ * (csrc/uprop_mc.hip).  means[b, k] (k >= 1) is the sample mean, summed in particle order and
+ * divided by n_samples; covs[b, k] the sample covariance over n_samples - 1, exactly
+ * symmetric; row 0 of both is x0 and S0 (NULL: s0_diag I).  particles (batch x (N+1) x
+ * n_samples x 7; row 0 = particles0) or NULL: the paths are not read back.  gp, exact, dt,
+ * alpha, g3, x0, U as gpmpc_uprop3_unscented, without its cap on the row count.  Nothing
+ * can fail per trajectory: no info.  (ABI 4: an added entry point.) */
+int gpmpc_uprop3_mc(gpmpc_ctx *ctx, void *gp, int exact, int batch, int N, int n_samples,
+                    double dt, double alpha, const double *g3,
+                    const double *x0, const double *U, const double *S0, double s0_diag,
+                    const double *particles0, const double *normals,
+                    double *means, double *covs, double *particles /* nullable */);
+/* The same for the 14-state model: RK4 with quaternion normalisation (rocket_6dof.py step)
+ * plus (d + sqrt(var) z) dt on rows 4-6 (d_v) and 11-13 (d_omega), one posterior per GP and
+ * step.  normals (batch x N x n_samples x 2 x 3): per particle the d_v normals, then the
+ * d_omega ones; particles0 and particles 14 wide.  gp_v / gp_w, exact and rocket as
+ * gpmpc_uprop6_linear.  (ABI 4: an added entry point.) */
+int gpmpc_uprop6_mc(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact, const double *rocket,
+                    int batch, int N, int n_samples, double dt,
+                    const double *x0, const double *U, const double *S0, double s0_diag,
+                    const double *particles0, const double *normals,
+                    double *means, double *covs, double *particles /* nullable */);
 
 /* ---- BASELINE configs[4]: batched 6-DoF GP-MPC rollouts --------------------
  * gpmpc_rollout_batched of SURVEY 8b.  One step = for every running rollout:

@@ -29,6 +29,11 @@ through gpurun, alone or under scripts/profile.sh for a kernel trace / PMC pass)
                             against the per-step host loop (use_device = False), back to back, at
                             B = 1 / 64, N = 20: the 3-DoF model (exact n = 1000, default FITC) and the
                             14-state model (exact n = 1000, FITC M = 50 and M = 2000) (JSON lines)
+  mc [reps]                 UncertaintyPropagator.propagate_monte_carlo_batch, the whole call (host draws
+                            and the one device call) against the per-step host loop (use_device = False)
+                            in the same process, at B = 1 / 64, N = 20, S = 100 / 4096 particles (host
+                            loop at S = 100 only): the 3-DoF model (exact n = 1000, default FITC) and the
+                            14-state model (FITC M = 50, exact n = 1000) (JSON lines)
 """
 import json
 import os
@@ -593,7 +598,66 @@ def unscented(reps="5"):
             print(json.dumps(row), flush=True)
 
 
-COMMANDS = dict(unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
+def mc(reps="3"):
+    from gp_mpc_rocket_landing_amd.data import synthetic_training_data
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig, Rocket6DoFDynamics, create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    from gp_mpc_rocket_landing_amd.rollouts6 import fit_structured_gp, initial_conditions_6dof
+    reps = int(reps)
+    N = 20
+    X, U, D = synthetic_training_data(1000, seed=0)
+
+    def gp3(sparse):
+        np.random.seed(0)
+        g = Simple3DoFGP(use_sparse=sparse)
+        g.add_data(X, U, D); g.fit()
+        return g
+
+    legs = [("3dof", "exact n=1000", lambda: gp3(False)), ("3dof", "fitc M=50", lambda: gp3(True)),
+            ("6dof", "fitc M=50", lambda: fit_structured_gp(1000, 50)),
+            ("6dof", "exact n=1000", lambda: fit_structured_gp(1000, 50, use_sparse=False))]
+    for model, name, make in legs:
+        gp = make()
+        for B in (1, 64):
+            rs = np.random.RandomState(B)
+            if model == "3dof":
+                dyn = create_normalized_rocket()
+                X0 = _fleet().initial_conditions(B)
+                Uh = np.tile((-X0[:, 0:1] * np.array([-1.0, 0, 0]))[:, None, :], (1, N, 1)) * (1 + 0.1 * rs.randn(B, N, 1))
+            else:
+                dyn = Rocket6DoFDynamics(Rocket6DoFConfig())
+                X0 = initial_conditions_6dof(B)
+                Uh = np.zeros((B, N, 3))
+                Uh[:, :, 2] = 0.9 * X0[:, 0:1] * Rocket6DoFConfig().g0
+                Uh[:, :, :2] = 0.05 * rs.randn(B, N, 2)
+            p = UncertaintyPropagator(dyn, gp, method="monte_carlo")
+            for S in (100, 4096):
+                row = dict(probe="mc", model=model, gp=name, B=B, N=N, S=S)
+
+                def surface():   # the whole call: the draws on the host, then one device call (or the host loop)
+                    np.random.seed(1)
+                    return p.propagate_monte_carlo_batch(X0, Uh, None, 0.1, n_samples=S)
+
+                def draws():
+                    np.random.seed(1)
+                    return p._monte_carlo_draw(X0, None, N, S)
+
+                p.use_device = True
+                md, cd = surface()
+                row["device_ms"] = _median_ms(surface, reps)
+                row["draws_ms"] = _median_ms(draws, reps)   # the part of device_ms that is numpy's RNG
+                if S == 100:
+                    p.use_device = False
+                    t0 = time.perf_counter()
+                    mh, ch = surface()
+                    row["host_loop_ms"] = (time.perf_counter() - t0) * 1e3   # one run, no warm-up needed: numpy
+                    row["means_maxdiff"] = float(np.abs(md - mh).max())
+                    row["covs_maxdiff"] = float(np.abs(cd - ch).max())
+                print(json.dumps(row), flush=True)
+
+
+COMMANDS = dict(mc=mc, unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
                 append=append, chol=chol, potrf=potrf, potrf_streams=potrf_streams, syrk_fitc=syrk_fitc,
                 gemm_loop=gemm_loop, trsm=trsm, rollouts6=rollouts6, qp_sweep=qp_sweep, surface=surface,
                 surface6=surface6)
