@@ -190,6 +190,11 @@ _sig("gpmpc_nn_dist", _c, _vp, _dp, _c, _dp, _c, _c, _dp)
 _sig("gpmpc_select_diverse", _c, _vp, _dp, _c, _c, _dp, _c, ctypes.c_double, _c, _ip, _dp)
 _sig("gpmpc_kmeans_lloyd", _c, _vp, _dp, _c, _c, _dp, _c, _c, _dp, _ip, _ip, _dp, _ip)
 _sig("gpmpc_kmeans_tau", ctypes.c_double, _c)
+_sig("gpmpc_knn_create", _c, _vp, _dp, _c, _c, _dp, _dp, ctypes.POINTER(_vp))
+_sig("gpmpc_knn_destroy", _c, _vp)
+_sig("gpmpc_knn_query", _c, _vp, _c, _dp, _c, _c, ctypes.c_double, _dp, _ip, _dp, _ip, _ip)
+_sig("gpmpc_knn_interp", _c, _vp, _c, _dp, _c, _c, _c, _c, _c, ctypes.c_double, _dp, _dp, _ip)
+_sig("gpmpc_knn_plan", _c, _c, _c, _c, _c, _ip, _ip)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -232,7 +237,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_fleet_query_launches", "gpmpc_gemm_diag", "gpmpc_nn_dist", "gpmpc_select_diverse",
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
             "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
-            "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc"]
+            "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc", "gpmpc_knn_create",
+            "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan"]
 
 
 class HIPError(RuntimeError):
@@ -917,6 +923,95 @@ def kmeans_lloyd(ctx, X, C0, iters=10):
     _chk(_L.gpmpc_kmeans_lloyd(ctx.h, _d(X), n, d, _d(C0), k, iters, _d(C), _i(labels), _i(empties), _d(margin),
                                _i(unsafe)), "kmeans_lloyd")
     return C, labels.astype(np.int64), empties.astype(np.int64), float(margin[0]), int(unsafe[0])
+
+
+# ---- k-nearest-neighbour search over a resident set (csrc/knn.hip) -----------------
+# the kernels' shape constants (csrc/knn.hip; tests/test_knn_plan.py keeps them equal)
+KNN_MAXD = 32
+KNN_MAXK = 64          # the list a query keeps: one entry a lane
+KNN_Q = 2              # queries a wave serves at once (1 for a single query)
+KNN_PART_ROWS = 1024   # the least rows of a part of the split
+KNN_MAX_PARTS = 64
+KNN_TARGET_WG = 512    # the scan's grid is split up to this many workgroups
+KNN_KD, KNN_NUMPY = 0, 1   # the summation order of s^2: scipy's KD-tree, np.linalg.norm
+
+
+def knn_plan(n, d, B, k=KNN_MAXK):
+    """gpmpc_knn_plan (no device): (parts, q_per_wave) of a call of B queries over n rows."""
+    parts = np.zeros(1, np.int32); q = np.zeros(1, np.int32)
+    rc = _L.gpmpc_knn_plan(int(n), int(d), int(B), int(k), _i(parts), _i(q))
+    if rc:
+        _err(rc, "knn_plan")
+    return int(parts[0]), int(q[0])
+
+
+class KnnSet:
+    """A set of n rows resident on the device (gpmpc_knn): S (n, d) stored as given, q (n,)
+    the rows' cost-to-go and fuel_req (n,) the fuel a row needs, either may be None."""
+
+    def __init__(self, ctx, S, q=None, fuel_req=None):
+        S = f64(np.atleast_2d(S)); n, d = S.shape
+        _finite(S, "KnnSet: S")
+        bufs = []
+        for name, a in (("q", q), ("fuel_req", fuel_req)):
+            if a is not None:
+                a = f64(np.asarray(a).reshape(-1))
+                if a.size != n:
+                    raise ValueError(f"KnnSet: {n} rows, {a.size} {name}")
+                _finite(a, f"KnnSet: {name}")
+            bufs.append(a)
+        h = _vp()
+        _chk(_L.gpmpc_knn_create(ctx.h, _d(S), n, d, _d(bufs[0]) if q is not None else None,
+                                 _d(bufs[1]) if fuel_req is not None else None, ctypes.byref(h)), "knn_create")
+        self.h, self.ctx, self.n, self.d = h, ctx, n, d
+        self.has_q, self.has_fuel = q is not None, fuel_req is not None
+
+    def _queries(self, what, Xq, avail_fuel):
+        Xq = f64(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"{what}: the set has {self.d} features, the queries {Xq.shape[1]}")
+        _finite(Xq, f"{what}: Xq")
+        if avail_fuel is not None:
+            avail_fuel = f64(np.broadcast_to(np.asarray(avail_fuel, np.float64), (Xq.shape[0],)))
+            _finite(avail_fuel, f"{what}: avail_fuel")
+        return Xq, avail_fuel
+
+    def query(self, Xq, k, radius=0.0, avail_fuel=None, order=KNN_KD):
+        """gpmpc_knn_query -> idx (B, k) int64 (n where fewer than k rows qualify), dist (B, k),
+        n_ball (B,), n_feasible (B,)."""
+        Xq, av = self._queries("knn_query", Xq, avail_fuel)
+        if not np.isfinite(radius):
+            raise ValueError("knn_query: radius must be finite")
+        B, k = Xq.shape[0], int(k)
+        m = max(k, 0)
+        idx = np.zeros((B, m), np.int32); dist = np.empty((B, m))
+        nb = np.zeros(B, np.int32); nf = np.zeros(B, np.int32)
+        _chk(_L.gpmpc_knn_query(self.h, int(order), _d(Xq), B, k, float(radius), _d(av) if av is not None else None,
+                                _i(idx), _d(dist), _i(nb), _i(nf)), "knn_query")
+        return idx.astype(np.int64), dist, nb.astype(np.int64), nf.astype(np.int64)
+
+    def interp(self, Xq, k_base, k_min, k_max, adaptive, radius, avail_fuel=None, order=KNN_KD):
+        """gpmpc_knn_interp -> q_out (B,), k_used (B,) int64: LocalSafeSet.interpolate_q with
+        inverse-distance weights, the K rule included (k_used -1: fewer rows than K)."""
+        Xq, av = self._queries("knn_interp", Xq, avail_fuel)
+        if not np.isfinite(radius):
+            raise ValueError("knn_interp: radius must be finite")
+        B = Xq.shape[0]
+        out = np.empty(B); used = np.zeros(B, np.int32)
+        _chk(_L.gpmpc_knn_interp(self.h, int(order), _d(Xq), B, int(k_base), int(k_min), int(k_max), int(bool(adaptive)),
+                                 float(radius), _d(av) if av is not None else None, _d(out), _i(used)), "knn_interp")
+        return out, used.astype(np.int64)
+
+    def close(self):
+        if self.h:
+            _L.gpmpc_knn_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---- diagnostic: the internal GEMM launchers (gpmpc_gemm_diag) -----------------

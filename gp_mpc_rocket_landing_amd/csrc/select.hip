@@ -17,8 +17,9 @@
 //
 // The whole file is compiled with contraction off: hipcc's default fuses a product into a
 // following sum, also through the header's __dmul_rn / __dadd_rn (plain operators there),
-// so the rounded operations are the local mul_rn / add_rn / sub_rn below.
+// so the rounded operations are sqdist.h's mul_rn / add_rn / sub_rn.
 #include "internal.h"
+#include "sqdist.h"
 #include <climits>
 #include <cmath>
 
@@ -36,39 +37,7 @@
 // automatic path: one workgroup up to this n, the grid above it (docs/PERF_HISTORY.md)
 #define SEL_CROSSOVER 6144
 
-__device__ __forceinline__ double mul_rn(double a, double b) { return a * b; }
-__device__ __forceinline__ double add_rn(double a, double b) { return a + b; }
-__device__ __forceinline__ double sub_rn(double a, double b) { return a - b; }
-
-// |x - y|^2 in numpy's order; y(k) reads element k of the other row
-template <int D, class Y>
-__device__ __forceinline__ double sqdist(const double (&x)[D], Y y) {
-  double s[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const double df = sub_rn(y(k), x[k]);
-    s[k] = mul_rn(df, df);
-  }
-  if constexpr (D < 8) {
-    double res = s[0];
-#pragma unroll
-    for (int k = 1; k < D; ++k) res = add_rn(res, s[k]);
-    return res;
-  } else {
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = s[j];
-#pragma unroll
-    for (int b = 8; b + 8 <= D; b += 8)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r[j] = add_rn(r[j], s[b + j]);
-    double res = add_rn(add_rn(add_rn(r[0], r[1]), add_rn(r[2], r[3])),
-                        add_rn(add_rn(r[4], r[5]), add_rn(r[6], r[7])));
-#pragma unroll
-    for (int k = D - D % 8; k < D; ++k) res = add_rn(res, s[k]);
-    return res;
-  }
-}
+// mul_rn / add_rn / sub_rn and sqdist (|x - y|^2 in numpy's order) are sqdist.h's, shared with knn.hip
 
 // ---------------------------------------------------------------------------
 // dist[i] = min_j |X[i] - R[j]|: one candidate per thread (its row in registers), the

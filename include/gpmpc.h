@@ -39,6 +39,7 @@ extern "C" {
 
 typedef struct gpmpc_ctx gpmpc_ctx;
 typedef struct gpmpc_gp gpmpc_gp;
+typedef struct gpmpc_knn gpmpc_knn;
 typedef struct gpmpc_fitc gpmpc_fitc;
 typedef struct gpmpc_fleet gpmpc_fleet;
 
@@ -767,6 +768,46 @@ int gpmpc_select_diverse(gpmpc_ctx *ctx, const double *X, int n, int d, const do
 int gpmpc_kmeans_lloyd(gpmpc_ctx *ctx, const double *X, int n, int d, const double *C0, int k, int iters,
                        double *C_out, int *labels_out, int *empty_per_iter, double *min_margin, int *unsafe);
 double gpmpc_kmeans_tau(int d);
+
+/* ---- k-nearest-neighbour search over a resident set -----------
+ * The neighbour search of the learning-MPC safe sets: LocalSafeSet.query / interpolate_q
+ * (local_safe_set.py:158-300) and the K neighbours of the Q-function approximators
+ * (q_function.py:97-190), batched over B queries against a set that stays on the device.
+ *
+ * gpmpc_knn_create: S n x d (host, row-major; stored as given, the caller applies any
+ * weighting), q (n, may be NULL) the rows' cost-to-go, fuel_req (n, may be NULL) the fuel a
+ * row needs.  1 <= d <= 32, n >= 1, else -2.
+ *
+ * gpmpc_knn_query, per query b (Xq B x d host): the k smallest distances in ascending order
+ * (dist, B x k) with their row indices (idx, B x k; positions in the full set), equal
+ * distances by lower row index; where fewer than k rows qualify the tail is inf / n.
+ * n_ball[b] = qualifying rows with s^2 <= radius * radius (the product rounded once, rows at
+ * the radius counted).  avail_fuel (B, may be NULL): row i qualifies iff fuel_req[i] <=
+ * avail_fuel[b] (without it every row does); n_feasible[b] = qualifying rows.  1 <= k <= 64,
+ * else -2.  Every s^2 is a sum of squared direct differences in the order `order` names:
+ * 0 scipy's KD-tree (four accumulators over full blocks of four, ((a0+a1)+a2)+a3, the tail
+ * one by one: KDTree.query's and query_ball_point's bits), 1 numpy's
+ * np.linalg.norm(A - x, axis=1) (as gpmpc_nn_dist); selection is on s^2, the square root is
+ * the correctly rounded one.
+ *
+ * gpmpc_knn_interp: LocalSafeSet.interpolate_q(method="inverse_distance") per query: K =
+ * k_base, with adaptive != 0 K = (int)(k_base * (1 + 2 * n_ball / n_feasible)) clipped to
+ * [k_min, k_max]; then min with n_feasible, max with k_min, min with k_max (k_max <= 64);
+ * q_out[b] = q of the nearest when its distance < 1e-10, else the mean of the K nearest q
+ * weighted by 1 / (dist + 1e-10); k_used[b] = K.  No qualifying row: q_out = inf, k_used = 0;
+ * fewer than K qualifying rows (the reference raises IndexError): q_out = NaN, k_used = -1.
+ *
+ * gpmpc_knn_plan (no device): how a call of B queries over n rows is launched: parts = the
+ * row ranges the scan's grid splits n into (> 1: a second launch merges them), q_per_wave =
+ * the queries a wave serves at once. */
+int gpmpc_knn_create(gpmpc_ctx *ctx, const double *S, int n, int d, const double *q, const double *fuel_req,
+                     gpmpc_knn **out);
+int gpmpc_knn_destroy(gpmpc_knn *set);
+int gpmpc_knn_query(gpmpc_knn *set, int order, const double *Xq, int B, int k, double radius,
+                    const double *avail_fuel, int *idx, double *dist, int *n_ball, int *n_feasible);
+int gpmpc_knn_interp(gpmpc_knn *set, int order, const double *Xq, int B, int k_base, int k_min, int k_max,
+                     int adaptive, double radius, const double *avail_fuel, double *q_out, int *k_used);
+int gpmpc_knn_plan(int n, int d, int B, int k, int *parts, int *q_per_wave);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,13 @@ through gpurun, alone or under scripts/profile.sh for a kernel trace / PMC pass)
                             in the same process, at B = 1 / 64, N = 20, S = 100 / 4096 particles (host
                             loop at S = 100 only): the 3-DoF model (exact n = 1000, default FITC) and the
                             14-state model (FITC M = 50, exact n = 1000) (JSON lines)
+  knn [reps]                gpmpc_knn_query (k = 64) and gpmpc_knn_interp (K_max = 50) over a resident
+                            set of n = 131072, d = 7 and n = 65536, d = 14 at B = 1 / 64 / 1024, whole
+                            calls, against the scipy loop the reference runs on the same box (one
+                            KDTree.query and one query_ball_point per state; the tree build apart); the
+                            plan of every shape and the whole-call fp64 rate; before them the query
+                            alone over small sets (n = 512 / 4096 / 16384, B = 1 ... 64) for the
+                            crossover between the two (JSON lines)
 """
 import json
 import os
@@ -657,7 +664,70 @@ def mc(reps="3"):
                 print(json.dumps(row), flush=True)
 
 
-COMMANDS = dict(mc=mc, unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
+def knn(reps="7"):
+    from scipy.spatial import KDTree
+    reps = int(reps)
+    ctx = _lib.default_context()
+    rng = np.random.default_rng(0)
+    # small sets, for the crossover of terminal/local_safe_set.py: the KD-tree answers them in
+    # microseconds, a device call never costs less than its launches and copies
+    for n, d in ((512, 7), (4096, 7), (16384, 7)):
+        S = np.cumsum(rng.standard_normal((n // 64, 64, d)) * 0.2, axis=1).reshape(n, d)
+        Xall = S[rng.choice(n, 64, replace=False)] + 0.05 * rng.standard_normal((64, d))
+        ks = _lib.KnnSet(ctx, S, rng.random(n))
+        tree = KDTree(S)
+        for B in (1, 2, 4, 8, 64):
+            X = Xall[:B]
+            parts, qw = _lib.knn_plan(n, d, B)
+            row = dict(probe="knn_small", n=n, d=d, B=B, parts=parts, q_per_wave=qw)
+            row["query_ms"] = _median_ms(lambda: ks.query(X, 64, 1.0), reps)
+
+            def scipy_small():
+                for x in X:
+                    tree.query(x, k=50)
+                    tree.query_ball_point(x, 1.0)
+            row["scipy_loop_ms"] = _median_ms(scipy_small, reps)
+            print(json.dumps(row), flush=True)
+        ks.close()
+    for n, d in ((131072, 7), (65536, 14)):
+        # a trajectory log in the small: correlated rows, the queries near stored rows
+        S = np.cumsum(rng.standard_normal((n // 64, 64, d)) * 0.2, axis=1).reshape(n, d)
+        q = rng.random(n)
+        Xall = S[rng.choice(n, 1024, replace=False)] + 0.05 * rng.standard_normal((1024, d))
+        t0 = time.perf_counter()
+        ks = _lib.KnnSet(ctx, S, q)
+        create_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        tree = KDTree(S)
+        build_ms = (time.perf_counter() - t0) * 1e3
+        print(json.dumps(dict(probe="knn_set", n=n, d=d, knn_create_ms=create_ms, kdtree_build_ms=build_ms)),
+              flush=True)
+        flops_row = 3 * d   # a difference, a square and an addition per feature and (query, row)
+        for B in (1, 64, 1024):
+            X = Xall[:B]
+            parts, qw = _lib.knn_plan(n, d, B)
+            row = dict(probe="knn", n=n, d=d, B=B, parts=parts, q_per_wave=qw)
+            row["query_ms"] = _median_ms(lambda: ks.query(X, 64, 1.0), reps)
+            row["interp_ms"] = _median_ms(lambda: ks.interp(X, 10, 4, 50, True, 1.0), reps)
+            row["query_gflops_whole_call"] = flops_row * n * B / (row["query_ms"][0] * 1e-3) / 1e9
+
+            def scipy_loop():
+                for x in X:
+                    tree.query(x, k=50)
+                    tree.query_ball_point(x, 1.0)
+            row["scipy_loop_ms"] = _median_ms(scipy_loop, reps)
+            idx, dist, nb, _ = ks.query(X[:16], 50, 1.0)
+            same = True
+            for b, x in enumerate(X[:16]):
+                dd, ii = tree.query(x, k=50)
+                same = same and np.array_equal(ii, idx[b]) and np.array_equal(dd, dist[b]) and \
+                    len(tree.query_ball_point(x, 1.0)) == nb[b]
+            row["equal_scipy_16"] = bool(same)
+            print(json.dumps(row), flush=True)
+        ks.close()
+
+
+COMMANDS = dict(knn=knn, mc=mc, unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
                 append=append, chol=chol, potrf=potrf, potrf_streams=potrf_streams, syrk_fitc=syrk_fitc,
                 gemm_loop=gemm_loop, trsm=trsm, rollouts6=rollouts6, qp_sweep=qp_sweep, surface=surface,
                 surface6=surface6)
