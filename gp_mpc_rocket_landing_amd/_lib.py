@@ -96,6 +96,16 @@ class FleetMCConfig(ctypes.Structure):
                 ("log_steps", ctypes.c_int)]
 
 
+class SafetyConfig(ctypes.Structure):
+    """gpmpc_safety_config: the predictive safety filter's backup law, ellipsoid and loop."""
+    _fields_ = [("horizon", ctypes.c_int), ("dt", ctypes.c_double), ("K", ctypes.c_double * 42),
+                ("P", ctypes.c_double * 196), ("x_eq", ctypes.c_double * 14), ("u_eq", ctypes.c_double * 3),
+                ("u_min", ctypes.c_double * 3), ("u_max", ctypes.c_double * 3), ("alpha", ctypes.c_double),
+                ("backup_margin", ctypes.c_double), ("have_constraints", ctypes.c_int), ("T_min", ctypes.c_double),
+                ("T_max", ctypes.c_double), ("cos_theta_max", ctypes.c_double), ("tan2_gamma", ctypes.c_double),
+                ("n_iters", ctypes.c_int), ("lr", ctypes.c_double), ("fd_eps", ctypes.c_double)]
+
+
 def _sig(name, res, *args):
     f = getattr(_L, name)
     f.restype = res
@@ -195,6 +205,9 @@ _sig("gpmpc_knn_destroy", _c, _vp)
 _sig("gpmpc_knn_query", _c, _vp, _c, _dp, _c, _c, ctypes.c_double, _dp, _ip, _dp, _ip, _ip)
 _sig("gpmpc_knn_interp", _c, _vp, _c, _dp, _c, _c, _c, _c, _c, ctypes.c_double, _dp, _dp, _ip)
 _sig("gpmpc_knn_plan", _c, _c, _c, _c, _c, _ip, _ip)
+_sig("gpmpc_safety_default_config", None, ctypes.POINTER(SafetyConfig))
+_sig("gpmpc_safety_filter", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip)
+_sig("gpmpc_safety_simulate", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -238,7 +251,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_gemm_row_tiles", "gpmpc_potrf_plan", "gpmpc_gram_path", "gpmpc_gemm_plan", "gpmpc_potrf_diag",
             "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
             "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc", "gpmpc_knn_create",
-            "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan"]
+            "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan",
+            "gpmpc_safety_default_config", "gpmpc_safety_filter", "gpmpc_safety_simulate"]
 
 
 class HIPError(RuntimeError):
@@ -1268,3 +1282,46 @@ def tri_diag(ctx, op, n, nrhs, L, X, W=None, flags=0):
         if ldw != n:
             raise ValueError("tri_diag: W is packed (ld n)")
     _chk(_L.gpmpc_tri_diag(ctx.h, opc, n, nrhs, pl, ldl, px, ldx, pw, int(flags)), "tri_diag")
+
+
+# ---- predictive safety filter (csrc/safety.hip) ----------------------------------------------
+def safety_default_config(**kw):
+    """gpmpc_safety_config at the library defaults with the keyword fields replaced (array
+    fields take any sequence of the right size)."""
+    c = SafetyConfig()
+    _L.gpmpc_safety_default_config(ctypes.byref(c))
+    return set_fields(c, kw)
+
+
+def safety_filter(ctx, rocket, cfg, X, U_nom):
+    """gpmpc_safety_filter: the predictive safety filter at B states X (B, 14) with nominal
+    controls U_nom (B, 3) in one device call.  rocket: 17 doubles as uprop6_linear; cfg: a
+    SafetyConfig -> u_safe (B, 3), margin (B,), backup_value (B,), flags (B,; bit 0 modified,
+    bit 1 safe), viol_mask (B,; bit 0 immediate, bit 1 + k path_k), iters (B,)."""
+    X = f64(np.atleast_2d(X)); U_nom = f64(np.atleast_2d(U_nom))
+    B = X.shape[0]
+    if B and (X.shape != (B, 14) or U_nom.shape != (B, 3)):
+        raise ValueError(f"safety_filter: shapes X {X.shape}, U_nom {U_nom.shape}")
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    u_safe = np.empty((B, 3)); margin = np.empty(B); value = np.empty(B)
+    flags = np.zeros(B, np.int32); mask = np.zeros(B, np.int32); iters = np.zeros(B, np.int32)
+    _chk(_L.gpmpc_safety_filter(ctx.h, _d(rk), ctypes.byref(cfg), B, _d(X), _d(U_nom), _d(u_safe), _d(margin),
+                                _d(value), _i(flags), _i(mask), _i(iters)), "safety_filter")
+    return u_safe, margin, value, flags, mask, iters
+
+
+def safety_simulate(ctx, rocket, cfg, X0, U_nom):
+    """gpmpc_safety_simulate: the closed loop filter -> plant step of B starts X0 (B, 14) over
+    the nominal controls U_nom (B, T, 3) in one device call -> X (B, T+1, 14), U (B, T, 3),
+    margin, flags, iters (each (B, T))."""
+    X0 = f64(np.atleast_2d(X0)); U_nom = f64(U_nom)
+    B = X0.shape[0]
+    if U_nom.ndim != 3 or (B and (X0.shape != (B, 14) or U_nom.shape[::2] != (B, 3))):
+        raise ValueError(f"safety_simulate: shapes X0 {X0.shape}, U_nom {U_nom.shape}")
+    T = U_nom.shape[1]
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    X = np.empty((B, T + 1, 14)); U = np.empty((B, T, 3)); margin = np.empty((B, T))
+    flags = np.zeros((B, T), np.int32); iters = np.zeros((B, T), np.int32)
+    _chk(_L.gpmpc_safety_simulate(ctx.h, _d(rk), ctypes.byref(cfg), B, T, _d(X0), _d(U_nom), _d(X), _d(U),
+                                  _d(margin), _i(flags), _i(iters)), "safety_simulate")
+    return X, U, margin, flags, iters

@@ -809,6 +809,60 @@ int gpmpc_knn_interp(gpmpc_knn *set, int order, const double *Xq, int B, int k_b
                      int adaptive, double radius, const double *avail_fuel, double *q_out, int *k_used);
 int gpmpc_knn_plan(int n, int d, int B, int k, int *parts, int *q_per_wave);
 
+/* ---- predictive safety filter ----------------------------------
+ * PredictiveSafetyFilter.filter of the reference's src/safety/safety_filter.py on its
+ * gradient path (_solve_gradient_qp), for the 14-state rocket under the linear backup law
+ * u = clip(u_eq - K (x - x_eq), u_min, u_max) and the ellipsoid V(x) = (x - x_eq)' P (x - x_eq)
+ * <= alpha.  A control is safe when (x, u) meets the constraints, the trajectory "u for one
+ * step, then the backup law" (horizon RK4 steps of dt) meets them at every step, and alpha -
+ * V(x_N) > 0.  An unsafe control takes at most n_iters steps u <- u - lr (grad V + 2 (u -
+ * u_nom)) with forward differences of fd_eps, each projected onto T_min <= |u| <= T_max (the
+ * lower side divides by max(|u|, 1e-6)), until V(x_N(u)) <= backup_margin * alpha.
+ *
+ * K 3 x 14 and P 14 x 14 row-major, any values (P is read as given, both triangles).
+ * u_min / u_max: -inf / +inf for no bound.  have_constraints = 0: no constraint test (the
+ * projection still uses T_min, T_max); else |u| in [T_min, T_max], 1 - 2 (qx^2 + qy^2) >=
+ * cos_theta_max and, above 0.1 of altitude, r_x^2 tan2_gamma >= r_y^2 + r_z^2.
+ * rocket: 17 doubles, J_B (9, row-major), r_T_B (3), g_I (3), alpha, g0 (gpmpc_uprop6_linear).
+ *
+ * gpmpc_safety_filter: batch queries x (batch x 14), u_nom (batch x 3), host buffers, one
+ * upload, one device call, one read-back.  Per query: u_safe (3), margin = alpha - V and
+ * backup_value = V of the returned control's trajectory, flags (bit 0: modified, bit 1: the
+ * returned control is safe), viol_mask (bit 0: the immediate test failed, bit 1 + k: step k of
+ * the path), iters (gradient steps taken; 0 when unmodified).
+ * gpmpc_safety_simulate: the closed loop x_(t+1) = step(x_t, filter(x_t, U_nom[t])) for T
+ * steps from batch starts x0 in one device call: X (batch x (T+1) x 14), U (batch x T x 3),
+ * margin / flags / iters (batch x T).
+ * Both return -2 with gpmpc_last_error set for a null pointer, batch < 1, horizon outside
+ * 1..31, dt <= 0 or a singular rocket J_B. */
+typedef struct {
+  int horizon;            /* 10 */
+  double dt;              /* 0.1 */
+  double K[42];
+  double P[196];
+  double x_eq[14];
+  double u_eq[3];
+  double u_min[3];        /* -inf */
+  double u_max[3];        /* +inf */
+  double alpha;           /* 1.0 */
+  double backup_margin;   /* 0.9 */
+  int have_constraints;   /* 0 */
+  double T_min;           /* 0.5 */
+  double T_max;           /* 5.0 */
+  double cos_theta_max;   /* cos 60 deg */
+  double tan2_gamma;      /* tan^2 30 deg */
+  int n_iters;            /* 50 */
+  double lr;              /* 0.1 */
+  double fd_eps;          /* 1e-4 */
+} gpmpc_safety_config;
+void gpmpc_safety_default_config(gpmpc_safety_config *cfg);
+int gpmpc_safety_filter(gpmpc_ctx *ctx, const double *rocket, const gpmpc_safety_config *cfg, int batch,
+                        const double *x, const double *u_nom, double *u_safe, double *margin,
+                        double *backup_value, int *flags, int *viol_mask, int *iters);
+int gpmpc_safety_simulate(gpmpc_ctx *ctx, const double *rocket, const gpmpc_safety_config *cfg, int batch, int T,
+                          const double *x0, const double *U_nom, double *X, double *U, double *margin, int *flags,
+                          int *iters);
+
 #ifdef __cplusplus
 }
 #endif
