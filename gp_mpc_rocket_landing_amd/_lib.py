@@ -205,6 +205,12 @@ _sig("gpmpc_knn_destroy", _c, _vp)
 _sig("gpmpc_knn_query", _c, _vp, _c, _dp, _c, _c, ctypes.c_double, _dp, _ip, _dp, _ip, _ip)
 _sig("gpmpc_knn_interp", _c, _vp, _c, _dp, _c, _c, _c, _c, _c, ctypes.c_double, _dp, _dp, _ip)
 _sig("gpmpc_knn_plan", _c, _c, _c, _c, _c, _ip, _ip)
+_sig("gpmpc_hull_project", _c, _vp, _dp, _dp, _ip, _c, _dp, _c, _c, _c, ctypes.c_double, _c, _dp, _dp, _dp, _dp, _dp,
+     _ip, _ip)
+_sig("gpmpc_knn_set_points", _c, _vp, _dp, _c)
+_sig("gpmpc_knn_hull", _c, _vp, _c, _dp, _dp, _c, _c, _c, _c, _c, ctypes.c_double, _dp, ctypes.c_double, _c, _ip, _ip,
+     _dp, _dp, _dp, _dp, _dp, _ip, _ip)
+_sig("gpmpc_hull_plan", _c, _c, _c, _c, _ip)
 _sig("gpmpc_safety_default_config", None, ctypes.POINTER(SafetyConfig))
 _sig("gpmpc_safety_filter", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip)
 _sig("gpmpc_safety_simulate", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip)
@@ -252,6 +258,7 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_tri_diag", "gpmpc_uprop3_unscented", "gpmpc_uprop6_unscented", "gpmpc_kmeans_lloyd",
             "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc", "gpmpc_knn_create",
             "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan",
+            "gpmpc_hull_project", "gpmpc_knn_set_points", "gpmpc_knn_hull", "gpmpc_hull_plan",
             "gpmpc_safety_default_config", "gpmpc_safety_filter", "gpmpc_safety_simulate"]
 
 
@@ -959,6 +966,62 @@ def knn_plan(n, d, B, k=KNN_MAXK):
     return int(parts[0]), int(q[0])
 
 
+# ---- projection onto a convex hull (csrc/hull.hip) ----------------------------------
+# the kernel's shape constants (csrc/hull.h; tests/test_hull_host.py keeps them equal)
+HULL_MAXD = 32
+HULL_MAXK = 64
+HULL_WAVES = 4         # queries a workgroup serves: one a wave
+HULL_MAX_ITER = 4096   # the most cycles a call may ask for, and the wrappers' default
+HULL_TOL = 1e-12       # the wrappers' default stop tolerance on the relative gap
+HULL_STATUS = {0: "certified", 1: "not certified", 2: "empty vertex set", 3: "non-finite input"}
+
+
+def hull_plan(d, kmax, B):
+    """gpmpc_hull_plan (no device): the queries one workgroup serves."""
+    q = np.zeros(1, np.int32)
+    rc = _L.gpmpc_hull_plan(int(d), int(kmax), int(B), _i(q))
+    if rc:
+        _err(rc, "hull_plan")
+    return int(q[0])
+
+
+def _hull_outputs(B, kmax, d):
+    return {"lam": np.zeros((B, kmax)), "proj": np.empty((B, d)), "dist": np.empty(B), "gap": np.empty(B),
+            "iters": np.zeros(B, np.int32), "status": np.zeros(B, np.int32)}
+
+
+def _hull_finish(out):
+    out["iters"] = out["iters"].astype(np.int64); out["status"] = out["status"].astype(np.int64)
+    return out
+
+
+def hull_project(ctx, V, X, q=None, nv=None, tol=HULL_TOL, max_iter=HULL_MAX_ITER):
+    """gpmpc_hull_project: every row of X (B, d) projected onto the hull of its vertex set ->
+    dict(lam (B, kmax), proj (B, d), dist, gap, qhull (None without q), iters, status).  V
+    (kmax, d): one set for all queries; V (B, kmax, d): a set a query, of which query b uses its
+    first nv[b] rows (nv None: all).  q: the vertices' values, shaped as V without its last axis."""
+    V = f64(V); X = f64(np.atleast_2d(X))
+    B, d = X.shape
+    shared = V.ndim == 2
+    if V.ndim not in (2, 3) or V.shape[-1] != d or (not shared and V.shape[0] != B):
+        raise ValueError(f"hull_project: V is {V.shape}, X {X.shape}")
+    kmax = V.shape[-2]
+    if q is not None:
+        q = f64(q)
+        if q.shape != V.shape[:-1]:
+            raise ValueError(f"hull_project: q is {q.shape}, expected {V.shape[:-1]}")
+    if nv is not None:
+        nv = np.ascontiguousarray(np.broadcast_to(np.asarray(nv), (B,)), dtype=np.int32)
+    out = _hull_outputs(B, kmax, d)
+    qh = np.empty(B)
+    _chk(_L.gpmpc_hull_project(ctx.h, _d(V), _d(q) if q is not None else None, _i(nv) if nv is not None else None,
+                               int(shared), _d(X), B, kmax, d, float(tol), int(max_iter), _d(out["lam"]),
+                               _d(out["proj"]), _d(out["dist"]), _d(out["gap"]), _d(qh) if q is not None else None,
+                               _i(out["iters"]), _i(out["status"])), "hull_project")
+    out["qhull"] = qh if q is not None else None
+    return _hull_finish(out)
+
+
 class KnnSet:
     """A set of n rows resident on the device (gpmpc_knn): S (n, d) stored as given, q (n,)
     the rows' cost-to-go and fuel_req (n,) the fuel a row needs, either may be None."""
@@ -979,6 +1042,7 @@ class KnnSet:
                                  _d(bufs[1]) if fuel_req is not None else None, ctypes.byref(h)), "knn_create")
         self.h, self.ctx, self.n, self.d = h, ctx, n, d
         self.has_q, self.has_fuel = q is not None, fuel_req is not None
+        self.dp = 0   # features of the payload rows (set_points), 0 without them
 
     def _queries(self, what, Xq, avail_fuel):
         Xq = f64(np.atleast_2d(Xq))
@@ -1015,6 +1079,39 @@ class KnnSet:
         _chk(_L.gpmpc_knn_interp(self.h, int(order), _d(Xq), B, int(k_base), int(k_min), int(k_max), int(bool(adaptive)),
                                  float(radius), _d(av) if av is not None else None, _d(out), _i(used)), "knn_interp")
         return out, used.astype(np.int64)
+
+    def set_points(self, P):
+        """gpmpc_knn_set_points: the payload rows P (n, dp) that ``hull`` takes its vertices from."""
+        P = f64(np.atleast_2d(P))
+        if P.shape[0] != self.n:
+            raise ValueError(f"knn_set_points: {self.n} rows, {P.shape[0]} payload rows")
+        _finite(P, "knn_set_points: P")
+        _chk(_L.gpmpc_knn_set_points(self.h, _d(P), P.shape[1]), "knn_set_points")
+        self.dp = P.shape[1]
+
+    def hull(self, Xq, Xp, k_base, k_min, k_max, adaptive, radius, avail_fuel=None, order=KNN_KD, tol=HULL_TOL,
+             max_iter=HULL_MAX_ITER):
+        """gpmpc_knn_hull -> the dict of ``hull_project`` plus k_used (B,) and idx (B, k_max) int64:
+        the search for Xq, the K rule, and the projection of Xp (B, dp) onto the hull of the K
+        nearest payload rows in one call."""
+        Xq, av = self._queries("knn_hull", Xq, avail_fuel)
+        if not np.isfinite(radius):
+            raise ValueError("knn_hull: radius must be finite")
+        B, km, dp = Xq.shape[0], max(int(k_max), 0), self.dp
+        Xp = f64(np.atleast_2d(Xp))
+        if dp and Xp.shape != (B, dp):
+            raise ValueError(f"knn_hull: Xp is {Xp.shape}, expected {(B, dp)}")
+        out = _hull_outputs(B, km, max(dp, 1))
+        used = np.zeros(B, np.int32); idx = np.zeros((B, km), np.int32)
+        qh = np.full(B, np.nan)
+        _chk(_L.gpmpc_knn_hull(self.h, int(order), _d(Xq), _d(Xp), B, int(k_base), int(k_min), int(k_max),
+                               int(bool(adaptive)), float(radius), _d(av) if av is not None else None, float(tol),
+                               int(max_iter), _i(used), _i(idx), _d(out["lam"]), _d(out["proj"]), _d(out["dist"]),
+                               _d(out["gap"]), _d(qh) if self.has_q else None, _i(out["iters"]), _i(out["status"])),
+             "knn_hull")
+        out["qhull"] = qh if self.has_q else None
+        out["k_used"] = used.astype(np.int64); out["idx"] = idx.astype(np.int64)
+        return _hull_finish(out)
 
     def close(self):
         if self.h:

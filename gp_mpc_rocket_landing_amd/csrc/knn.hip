@@ -25,6 +25,7 @@
 // large n the rows are split over P parts (grid.y) and a second launch merges the P lists of
 // a query; the order between the launches is the kernel boundary alone.
 #include "internal.h"
+#include "hull.h"
 #include "sqdist.h"
 #include <climits>
 #include <cmath>
@@ -49,6 +50,8 @@ struct gpmpc_knn {
   gpmpc_ctx *ctx = nullptr;
   int n = 0, d = 0;
   DevBuf St, q, fuel;  // St: d x n feature-major; q, fuel: n or unallocated
+  int dp = 0;
+  DevBuf P;            // n x dp payload rows (gpmpc_knn_set_points), or unallocated
 };
 
 // (sa, ia) before (sb, ib) in the total order: by s^2, then by row index
@@ -350,16 +353,10 @@ __global__ __launch_bounds__(64) void k_knn_emit(const double *__restrict__ fin_
   }
 }
 
-// LocalSafeSet.interpolate_q(method="inverse_distance") from the final lists: the K rule of
-// LocalSafeSet.query (local_safe_set.py:182-213, 236-249) and the weighting (:279-287), one wave
-// a query.  k_used = -1 (q_out NaN) where the reference raises (fewer available rows than K).
-__global__ __launch_bounds__(64) void k_knn_interp(const double *__restrict__ fin_s, const int *__restrict__ fin_i,
-                                                   const int *__restrict__ fin_cnt, const double *__restrict__ qv,
-                                                   int k_base, int k_min, int k_max, int adaptive,
-                                                   double *__restrict__ q_out, int *__restrict__ k_used) {
-  const int64_t b = blockIdx.x;
-  const int j = threadIdx.x;
-  const int nball = fin_cnt[b * 2], navail = fin_cnt[b * 2 + 1];
+// The K rule of LocalSafeSet.query (local_safe_set.py:182-213, 236-249) from a query's ball and
+// available counts: K; 0 without a safe state; -1 where the reference raises (fewer available
+// rows than K).  The one place it lives on the device (k_knn_interp, k_knn_hull_prep).
+__device__ __forceinline__ int knn_k_rule(int nball, int navail, int k_base, int k_min, int k_max, int adaptive) {
   int K = k_base;
   if (navail > 0 && adaptive) {
     const double dens = (double)nball / (double)navail;
@@ -370,14 +367,28 @@ __global__ __launch_bounds__(64) void k_knn_interp(const double *__restrict__ fi
   K = K < navail ? K : navail;
   K = K > k_min ? K : k_min;
   K = K < k_max ? K : k_max;
-  if (navail == 0 || K == 0) {  // no safe state: the reference returns inf
+  if (navail == 0 || K == 0) return 0;
+  return K > navail ? -1 : K;
+}
+
+// LocalSafeSet.interpolate_q(method="inverse_distance") from the final lists: the K rule of
+// LocalSafeSet.query (local_safe_set.py:182-213, 236-249) and the weighting (:279-287), one wave
+// a query.  k_used = -1 (q_out NaN) where the reference raises (fewer available rows than K).
+__global__ __launch_bounds__(64) void k_knn_interp(const double *__restrict__ fin_s, const int *__restrict__ fin_i,
+                                                   const int *__restrict__ fin_cnt, const double *__restrict__ qv,
+                                                   int k_base, int k_min, int k_max, int adaptive,
+                                                   double *__restrict__ q_out, int *__restrict__ k_used) {
+  const int64_t b = blockIdx.x;
+  const int j = threadIdx.x;
+  const int K = knn_k_rule(fin_cnt[b * 2], fin_cnt[b * 2 + 1], k_base, k_min, k_max, adaptive);
+  if (K == 0) {  // no safe state: the reference returns inf
     if (j == 0) {
       q_out[b] = INFINITY;
       k_used[b] = 0;
     }
     return;
   }
-  if (K > navail) {
+  if (K < 0) {
     if (j == 0) {
       q_out[b] = NAN;
       k_used[b] = -1;
@@ -614,6 +625,100 @@ extern "C" int gpmpc_knn_interp(gpmpc_knn *set, int order, const double *Xq, int
   hipLaunchKernelGGL(k_knn_interp, dim3((unsigned)B), dim3(64), 0, s, f.s, f.i, f.cnt, set->q.as<double>(), k_base,
                      k_min, k_max, adaptive, dq, dk);
   GPMPC_HIP(hipGetLastError());
+  GPMPC_HIP(sg.download());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The vertex sets of the fused hull call from the final lists: the K rule, then the K nearest
+// row indices, nearest first (idx: [B][k_max], n past K), nv = K (0 where k_used is 0 or -1).
+__global__ __launch_bounds__(64) void k_knn_hull_prep(const int *__restrict__ fin_i, const int *__restrict__ fin_cnt,
+                                                      int n, int k_base, int k_min, int k_max, int adaptive,
+                                                      int *__restrict__ idx, int *__restrict__ nv,
+                                                      int *__restrict__ k_used) {
+  const int64_t b = blockIdx.x;
+  const int j = threadIdx.x;
+  const int K = knn_k_rule(fin_cnt[b * 2], fin_cnt[b * 2 + 1], k_base, k_min, k_max, adaptive);
+  const int used = K > 0 ? K : 0;
+  if (j < k_max) idx[b * k_max + j] = j < used ? fin_i[b * KNN_MAXK + j] : n;
+  if (j == 0) {
+    nv[b] = used;
+    k_used[b] = K;
+  }
+}
+
+extern "C" int gpmpc_knn_set_points(gpmpc_knn *set, const double *P, int dp) {
+  GPMPC_CHECK_ARG(set && set->ctx && P);
+  GPMPC_CHECK_ARG(dp >= 1 && dp <= HULL_MAXD);
+  GPMPC_HIP(hipSetDevice(set->ctx->device));
+  hipStream_t s = set->ctx->stream;
+  const size_t bytes = sizeof(double) * (size_t)set->n * dp;
+  set->dp = 0;
+  GPMPC_HIP(set->P.alloc(bytes));
+  GPMPC_HIP(hipMemcpyAsync(set->P.p, P, bytes, hipMemcpyHostToDevice, s));
+  GPMPC_HIP(hipStreamSynchronize(s));
+  set->dp = dp;
+  return 0;
+}
+
+extern "C" int gpmpc_knn_hull(gpmpc_knn *set, int order, const double *Xq, const double *Xp, int B, int k_base,
+                              int k_min, int k_max, int adaptive, double radius, const double *avail_fuel,
+                              double tol, int max_iter, int *k_used, int *idx, double *lambda, double *proj,
+                              double *dist, double *gap, double *qhull, int *iters, int *status) {
+  if (int rc = knn_check_call(set, order, Xq, B, radius, avail_fuel)) return rc;
+  GPMPC_CHECK_ARG(k_base >= 1 && k_min >= 0 && k_min <= k_max && k_max >= 1 && k_max <= KNN_MAXK);
+  GPMPC_CHECK_ARG(tol > 0.0 && tol < INFINITY);
+  GPMPC_CHECK_ARG(max_iter >= 1 && max_iter <= HULL_MAX_ITER);
+  GPMPC_CHECK_ARG(B == 0 || (Xp && k_used && idx && lambda && proj && dist && gap && iters && status));
+  if (!set->dp) {
+    gpmpc_set_error("knn_hull: the set has no payload rows (gpmpc_knn_set_points)");
+    return -2;
+  }
+  if (B == 0) return 0;
+  GPMPC_HIP(hipSetDevice(set->ctx->device));
+  hipStream_t s = set->ctx->stream;
+  const size_t nb = (size_t)B, d = (size_t)set->d, dp = (size_t)set->dp, km = (size_t)k_max;
+  const bool with_q = set->q.p && qhull;
+  Stage sg(s, Stage::pad(8 * nb * d) + 2 * Stage::pad(8 * nb * dp) + (avail_fuel ? Stage::pad(8 * nb) : 0) +
+                  5 * Stage::pad(4 * nb) + Stage::pad(4 * nb * km) + Stage::pad(8 * nb * km) + 3 * Stage::pad(8 * nb));
+  if (!sg.ok()) {
+    gpmpc_set_error("knn_hull: staging buffers: out of memory");
+    return -1;
+  }
+  const double *dXq = sg.in(Xq, nb * d);
+  const double *dXp = sg.in(Xp, nb * dp);
+  const double *dav = avail_fuel ? sg.in(avail_fuel, nb) : nullptr;
+  DevBuf nvbuf;  // the vertex counts stay on the device
+  GPMPC_HIP(nvbuf.alloc(s, sizeof(int) * nb));
+  int *dnv = nvbuf.as<int>();
+  HullArgs a{};
+  a.V = set->P.as<double>();
+  a.q = with_q ? set->q.as<double>() : nullptr;
+  a.X = dXp;
+  a.nv = dnv;
+  a.B = B;
+  a.kmax = k_max;
+  a.d = set->dp;
+  a.shared = 0;
+  a.tol = tol;
+  a.max_iter = max_iter;
+  int *dused = sg.out(k_used, nb);
+  int *didx = sg.out(idx, nb * km);
+  a.gidx = didx;
+  a.lambda = sg.out(lambda, nb * km);
+  a.proj = sg.out(proj, nb * dp);
+  a.dist = sg.out(dist, nb);
+  a.gap = sg.out(gap, nb);
+  a.qhull = with_q ? sg.out(qhull, nb) : nullptr;
+  a.iters = sg.out(iters, nb);
+  a.status = sg.out(status, nb);
+  GPMPC_HIP(sg.upload());
+  KnnFinal f;
+  if (int rc = knn_search(set, order, dXq, B, dav, radius, f)) return rc;
+  hipLaunchKernelGGL(k_knn_hull_prep, dim3((unsigned)B), dim3(64), 0, s, f.i, f.cnt, set->n, k_base, k_min, k_max,
+                     adaptive, didx, dnv, dused);
+  GPMPC_HIP(hipGetLastError());
+  GPMPC_HIP(launch_hull(s, a));
   GPMPC_HIP(sg.download());
   return 0;
 }

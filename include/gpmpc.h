@@ -809,6 +809,58 @@ int gpmpc_knn_interp(gpmpc_knn *set, int order, const double *Xq, int B, int k_b
                      int adaptive, double radius, const double *avail_fuel, double *q_out, int *k_used);
 int gpmpc_knn_plan(int n, int d, int B, int k, int *parts, int *q_per_wave);
 
+/* ---- projection onto a convex hull ------------------------------
+ * The terminal constraint x_N in Conv{v_1 .. v_K} of learning MPC: ConvexHullConstraint.
+ * project_onto_hull / check_feasibility / get_interpolated_q (convex_hull.py:125-237), batched
+ * over B queries.  Per query x and its nv <= 64 vertices in d <= 32 dimensions: lambda >= 0,
+ * sum lambda = 1, minimising |sum lambda_i w_i|, w_i = v_i - x, by Wolfe's minimum-norm-point
+ * method.  A major cycle takes the vertex that minimises p . w_i (p = sum lambda_i w_i; equal
+ * values: the lower index) into the active set unless |p|^2 - min_i p . w_i <= tol max_i |w_i|^2;
+ * a minor cycle moves to the minimum-norm point of the active set's affine hull, or towards it
+ * up to the boundary and drops the vertex that reaches zero.  The run starts at the vertex
+ * nearest x (the lowest such index) and takes at most max_iter cycles, major and minor counted
+ * alike.
+ *
+ * gpmpc_hull_project: shared = 1: one vertex set V (kmax x d, host, row-major) and q (kmax, may
+ * be NULL) for all B queries; shared = 0: V B x kmax x d and q B x kmax.  nv (B, may be NULL:
+ * kmax for every query): query b uses the first nv[b] rows of its set, rows past them are never
+ * read by the device.  X B x d.  Per query: lambda (B x kmax, zero past nv[b]), proj (B x d) =
+ * x + sum lambda_i w_i, dist = |proj - x|, gap = (|p|^2 - min_i p . w_i) / max_i |w_i|^2 (0
+ * where that maximum is 0), qhull = sum lambda_i q_i (written only when q is given), iters the
+ * cycles taken, status:
+ *   0 certified: the stop test holds in fp64;
+ *   1 not certified: max_iter reached, or the active set numerically dependent; lambda is
+ *     still a convex combination and gap says how far it is from certified;
+ *   2 nv[b] = 0: proj = x, dist = +inf, lambda 0, gap 0, qhull +inf;
+ *   3 a non-finite entry among x or the used vertices (or a difference whose square
+ *     overflows), tested before the first cycle: the outputs are NaN (lambda past nv[b] zero).
+ * The result of a query depends on its own x, nv[b] and used rows alone, bit for bit.
+ * 1 <= d <= 32, 1 <= kmax <= 64, 0 <= nv[b] <= kmax, tol > 0 (finite), 1 <= max_iter <= 4096,
+ * else -2; B = 0 returns 0.
+ *
+ * gpmpc_knn_set_points: attaches n x dp payload rows P (host, row-major, 1 <= dp <= 32) to a
+ * k-NN set: the raw states of the rows the set searches by (the set itself holds the weighted
+ * ones).  A second call replaces them; the other calls of the set do not read them.
+ *
+ * gpmpc_knn_hull: gpmpc_knn_query's search for Xq (B x d), the K rule of gpmpc_knn_interp, then
+ * the projection of Xp (B x dp) onto the hull of the K nearest payload rows, nearest first, in
+ * one call that does not leave the device in between.  k_used[b] = K (0 with status 2 when no
+ * row qualifies; -1, also status 2, where the reference raises IndexError), idx (B x k_max)
+ * the K row indices (n past K), lambda B x k_max, qhull from the set's q (may be NULL; written
+ * only when the set has q); the other outputs as gpmpc_hull_project, whose result on the same
+ * rows it equals bit for bit.  -2 without payload rows.
+ *
+ * gpmpc_hull_plan (no device): q_per_group = the queries one workgroup serves (one a wave). */
+int gpmpc_hull_project(gpmpc_ctx *ctx, const double *V, const double *q, const int *nv, int shared,
+                       const double *X, int B, int kmax, int d, double tol, int max_iter, double *lambda,
+                       double *proj, double *dist, double *gap, double *qhull, int *iters, int *status);
+int gpmpc_knn_set_points(gpmpc_knn *set, const double *P, int dp);
+int gpmpc_knn_hull(gpmpc_knn *set, int order, const double *Xq, const double *Xp, int B, int k_base, int k_min,
+                   int k_max, int adaptive, double radius, const double *avail_fuel, double tol, int max_iter,
+                   int *k_used, int *idx, double *lambda, double *proj, double *dist, double *gap, double *qhull,
+                   int *iters, int *status);
+int gpmpc_hull_plan(int d, int kmax, int B, int *q_per_group);
+
 /* ---- predictive safety filter ----------------------------------
  * PredictiveSafetyFilter.filter of the reference's src/safety/safety_filter.py on its
  * gradient path (_solve_gradient_qp), for the 14-state rocket under the linear backup law

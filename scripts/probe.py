@@ -41,6 +41,11 @@ through gpurun, alone or under scripts/profile.sh for a kernel trace / PMC pass)
                             plan of every shape and the whole-call fp64 rate; before them the query
                             alone over small sets (n = 512 / 4096 / 16384, B = 1 ... 64) for the
                             crossover between the two (JSON lines)
+  hull [reps] [device_only] TerminalSetManager.project_batch (gpmpc_knn_hull, one device call) for 1024
+                            states over safe sets of 4096 rows, 7 and 14 states, K = 10 and K = 50,
+                            against the numpy restatement of the contract (tests/hull_check.py) looped
+                            over the same vertex sets; with a second argument the device calls alone,
+                            for a kernel trace (JSON lines)
 """
 import json
 import os
@@ -727,7 +732,46 @@ def knn(reps="7"):
         ks.close()
 
 
-COMMANDS = dict(knn=knn, mc=mc, unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
+def hull(reps="7", device_only=""):
+    """TerminalSetManager.project_batch for 1024 states over safe sets of 4096 rows (7 and 14
+    states, K = 10 and K = 50), the fused device call against the numpy restatement of the
+    contract (tests/hull_check.py) looped over the same vertex sets.  device_only: the device
+    calls alone, for a kernel trace."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import hull_check as hc
+    from gp_mpc_rocket_landing_amd.terminal import SampledSafeSet, TerminalSetManager
+    reps = int(reps)
+    os.environ["GPMPC_KNN"] = "device"
+    rng = np.random.default_rng(0)
+    for n_x in (7, 14):
+        ss = SampledSafeSet(n_x=n_x, n_u=3)
+        for _ in range(64):   # a trajectory log in the small: 64 walks of 64 states
+            ss.add_trajectory(np.cumsum(rng.standard_normal((64, n_x)) * 0.2, axis=0), np.zeros((63, 3)), np.ones(63))
+        S = ss.get_all_states()
+        X = S[rng.choice(len(S), 1024, replace=False)] + 0.05 * rng.standard_normal((1024, n_x))
+        for K in (10, 50):
+            tm = TerminalSetManager(ss, n_vertices=K)
+            row = dict(probe="hull", n=len(S), n_x=n_x, B=len(X), K=K)
+            row["project_batch_ms"] = _median_ms(lambda: tm.project_batch(X), reps)
+            out = tm.project_batch(X)
+            row["status_counts"] = {int(k): int(v) for k, v in Counter(out["status"].tolist()).items()}
+            row["k_used"] = [int(out["k_used"].min()), int(out["k_used"].max())]
+            row["inside"] = int(np.sum(out["dist"] <= 1e-6))
+            if not device_only:
+                sets = [(S[out["idx"][b, :out["k_used"][b]]], X[b]) for b in range(len(X))]
+                res = []
+
+                def numpy_loop():
+                    res[:] = [hc.wolfe(V, x) for V, x in sets]
+                row["numpy_loop_ms"] = _median_ms(numpy_loop, min(reps, 3))
+                row["numpy_status_counts"] = {int(k): int(v) for k, v in Counter(r["status"] for r in res).items()}
+                row["max_cycles_numpy"] = int(max(r["iters"] for r in res))
+                row["max_rel_err_vs_numpy"] = float(max(hc.rel_err(out["proj"][b], res[b]["proj"], *sets[b])
+                                                        for b in range(len(X))))
+            print(json.dumps(row), flush=True)
+
+
+COMMANDS = dict(hull=hull, knn=knn, mc=mc, unscented=unscented, novelty=novelty, single=single, step=step, stamps=stamps, placement=placement, streams=streams, fit=fit,
                 append=append, chol=chol, potrf=potrf, potrf_streams=potrf_streams, syrk_fitc=syrk_fitc,
                 gemm_loop=gemm_loop, trsm=trsm, rollouts6=rollouts6, qp_sweep=qp_sweep, surface=surface,
                 surface6=surface6)
