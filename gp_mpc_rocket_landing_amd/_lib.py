@@ -214,6 +214,10 @@ _sig("gpmpc_hull_plan", _c, _c, _c, _c, _ip)
 _sig("gpmpc_safety_default_config", None, ctypes.POINTER(SafetyConfig))
 _sig("gpmpc_safety_filter", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip)
 _sig("gpmpc_safety_simulate", _c, _vp, _dp, ctypes.POINTER(SafetyConfig), _c, _c, _dp, _dp, _dp, _dp, _dp, _ip, _ip)
+_sig("gpmpc_tube_linear", _c, _vp, _dp, _c, _c, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _c, ctypes.c_double, _dp,
+     _dp, _dp, _dp)
+_sig("gpmpc_tube_mc", _c, _vp, _dp, _c, _c, _c, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _dp)
+_sig("gpmpc_tube_plan", _c, _c, _c, _ip, _ip)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -259,7 +263,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_kmeans_tau", "gpmpc_qp_pattern_info", "gpmpc_uprop3_mc", "gpmpc_uprop6_mc", "gpmpc_knn_create",
             "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan",
             "gpmpc_hull_project", "gpmpc_knn_set_points", "gpmpc_knn_hull", "gpmpc_hull_plan",
-            "gpmpc_safety_default_config", "gpmpc_safety_filter", "gpmpc_safety_simulate"]
+            "gpmpc_safety_default_config", "gpmpc_safety_filter", "gpmpc_safety_simulate",
+            "gpmpc_tube_linear", "gpmpc_tube_mc", "gpmpc_tube_plan"]
 
 
 class HIPError(RuntimeError):
@@ -1422,3 +1427,64 @@ def safety_simulate(ctx, rocket, cfg, X0, U_nom):
     _chk(_L.gpmpc_safety_simulate(ctx.h, _d(rk), ctypes.byref(cfg), B, T, _d(X0), _d(U_nom), _d(X), _d(U),
                                   _d(margin), _i(flags), _i(iters)), "safety_simulate")
     return X, U, margin, flags, iters
+
+
+# ---- tube MPC: uncertainty tubes (csrc/tube.hip) ------------------------------------------------
+def tube_plan(N=0, n_samples=0):
+    """gpmpc_tube_plan (no device): (k_tile, mc_cap): the horizon steps one pass of the linear
+    kernel takes and the largest n_samples tube_mc accepts."""
+    kt = np.zeros(1, np.int32); cap = np.zeros(1, np.int32)
+    rc = _L.gpmpc_tube_plan(int(N), int(n_samples), _i(kt), _i(cap))
+    if rc:
+        _err(rc, "tube_plan")
+    return int(kt[0]), int(cap[0])
+
+
+def _tube_traj(what, X_nom, U_nom):
+    X_nom = f64(X_nom); U_nom = f64(U_nom)
+    if X_nom.ndim != 3 or U_nom.ndim != 3 or X_nom.shape[2] != 14 or U_nom.shape[2] != 3 or (
+            X_nom.shape[0] != U_nom.shape[0] or X_nom.shape[1] != U_nom.shape[1] + 1):
+        raise ValueError(f"{what}: shapes X_nom {X_nom.shape}, U_nom {U_nom.shape}")
+    return X_nom, U_nom, X_nom.shape[0], U_nom.shape[1]
+
+
+def tube_linear(ctx, rocket, X_nom, U_nom, dt, eps=1e-6, w=None, w_max=0.1, K=None, return_AB=False):
+    """gpmpc_tube_linear: the linear tubes of B nominal trajectories X_nom (B, N+1, 14), U_nom
+    (B, N, 3) in one device call.  w: None (w_max on every row), (14,) or (B, N, 14); K: None or
+    (3, 14) -> tubes (B, N+1, 14), and with return_AB the linearisations A (B, N, 14, 14) and
+    B (B, N, 14, 3)."""
+    X_nom, U_nom, B, N = _tube_traj("tube_linear", X_nom, U_nom)
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    mode, wp = 0, None
+    if w is not None:
+        w = f64(w)
+        if w.shape not in ((14,), (B, N, 14)):
+            raise ValueError(f"tube_linear: w shape {w.shape}, expected (14,) or {(B, N, 14)}")
+        mode, wp = (1 if w.ndim == 1 else 2), _d(w)
+    Kp = None
+    if K is not None:
+        K = f64(K)
+        if K.shape != (3, 14):
+            raise ValueError(f"tube_linear: K shape {K.shape}, expected (3, 14)")
+        Kp = _d(K)
+    tubes = np.empty((B, N + 1, 14))
+    A = np.empty((B, N, 14, 14)) if return_AB else None
+    Bm = np.empty((B, N, 14, 3)) if return_AB else None
+    _chk(_L.gpmpc_tube_linear(ctx.h, _d(rk), B, N, float(dt), float(eps), _d(X_nom), _d(U_nom), wp, mode, float(w_max),
+                              Kp, _d(tubes), _d(A) if return_AB else None, _d(Bm) if return_AB else None),
+         "tube_linear")
+    return (tubes, A, Bm) if return_AB else tubes
+
+
+def tube_mc(ctx, rocket, X_nom, U_nom, noise, dt, quantile=0.95):
+    """gpmpc_tube_mc: the Monte-Carlo quantile tubes of B nominal trajectories over the
+    caller's draws noise (B, N, n_samples, 14) in one device call -> tubes (B, N+1, 14)."""
+    X_nom, U_nom, B, N = _tube_traj("tube_mc", X_nom, U_nom)
+    noise = f64(noise)
+    if noise.ndim != 4 or noise.shape[:2] != (B, N) or noise.shape[3] != 14:
+        raise ValueError(f"tube_mc: noise shape {noise.shape}, expected {(B, N)} x n_samples x 14")
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    tubes = np.empty((B, N + 1, 14))
+    _chk(_L.gpmpc_tube_mc(ctx.h, _d(rk), B, N, noise.shape[2], float(dt), float(quantile), _d(X_nom), _d(U_nom),
+                          _d(noise), _d(tubes)), "tube_mc")
+    return tubes

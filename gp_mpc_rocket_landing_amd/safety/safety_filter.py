@@ -6,7 +6,8 @@ one step, then the backup controller" meets them along the way, and its terminal
 inside the backup ellipsoid.  An unsafe u is replaced by the result of at most 50 projected
 gradient steps on V(x_N(u)) + |u - u_nom|^2 with forward-difference gradients (the reference's
 ``_solve_gradient_qp``, the path it takes without CasADi; the CasADi / IPOPT path is not
-restated).  ``tube_propagator`` is None: ``filter`` never reads it.
+restated).  ``tube_propagator`` is None: ``filter`` never reads it (the tubes are
+``tube_mpc.TubePropagator``'s).
 
 Additions: ``filter_batch`` and ``simulate_filtered_batch`` answer B queries (B closed loops)
 in one call, and every call is dispatched.  With ``Rocket6DoFDynamics``, an
@@ -38,6 +39,25 @@ def safety_mode() -> str:
     if mode not in ("", "host", "device"):
         raise ValueError(f"GPMPC_SAFETY={mode!r}: expected host or device")
     return mode
+
+
+def rocket_gate(dynamics) -> Optional[str]:
+    """None when csrc/fleet6.h's R6Rocket can express the plant (this package's
+    ``Rocket6DoFDynamics`` itself, with an invertible inertia tensor), else why not.  The gate the
+    safety filter and the tube propagator share."""
+    from ..dynamics.rocket_6dof import Rocket6DoFDynamics
+    if type(dynamics) is not Rocket6DoFDynamics:
+        return "the dynamics is not Rocket6DoFDynamics"
+    if not dynamics.matches_device_model():
+        return "the rocket is not one the device model runs"
+    return None
+
+
+def rocket_vector(dynamics) -> np.ndarray:
+    """The rocket's 17 doubles as the library takes them: J_B (9), r_T_B (3), g_I (3), alpha, g0."""
+    p = dynamics.params
+    return np.concatenate([np.asarray(p.J_B, float).reshape(9), np.asarray(p.r_T_B, float).reshape(3),
+                           np.asarray(p.g_I, float).reshape(3), [float(p.alpha), float(p.g0)]])
 
 
 @dataclass
@@ -140,7 +160,7 @@ class PredictiveSafetyFilter:
         self.n_u = 3
         self.backup = LQRBackupController(dynamics, BackupControllerConfig(dt=self.config.dt))
         self.invariant_set = EllipsoidalInvariantSet(self.n_x, InvariantSetConfig())
-        self.tube_propagator = None  # tube_mpc.py is not restated; filter() never reads it
+        self.tube_propagator = None  # as in the reference: filter() never reads it (tube_mpc.TubePropagator)
         self._gp_model = None
         self._initialized = False
         self.ctx = None              # a _lib.Context; None: the default context
@@ -303,13 +323,11 @@ class PredictiveSafetyFilter:
     def _device_gate(self) -> Tuple[bool, str]:
         """(True, why) when the device kernel restates this filter exactly, else (False, why).
         Host logic only: no device call."""
-        from ..dynamics.rocket_6dof import Rocket6DoFDynamics
         if safety_mode() == "host":
             return False, "GPMPC_SAFETY=host"
-        if type(self.dynamics) is not Rocket6DoFDynamics:
-            return False, "the dynamics is not Rocket6DoFDynamics"
-        if not self.dynamics.matches_device_model():
-            return False, "the rocket is not one the device model runs"
+        why = rocket_gate(self.dynamics)
+        if why is not None:
+            return False, why
         if type(self.backup) is not LQRBackupController:
             return False, "the backup controller is not LQRBackupController"
         b, s = self.backup, self.invariant_set
@@ -341,10 +359,7 @@ class PredictiveSafetyFilter:
         if self.constraint_params is not None:
             _, _, cos_theta_max, tan_gamma = self._constraint_values()
             kw.update(have_constraints=1, cos_theta_max=float(cos_theta_max), tan2_gamma=float(tan_gamma ** 2))
-        p = self.dynamics.params
-        rocket = np.concatenate([np.asarray(p.J_B, float).reshape(9), np.asarray(p.r_T_B, float).reshape(3),
-                                 np.asarray(p.g_I, float).reshape(3), [float(p.alpha), float(p.g0)]])
-        return _lib.safety_default_config(**kw), rocket
+        return _lib.safety_default_config(**kw), rocket_vector(self.dynamics)
 
     def _context(self):
         from .. import _lib

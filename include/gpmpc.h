@@ -915,6 +915,33 @@ int gpmpc_safety_simulate(gpmpc_ctx *ctx, const double *rocket, const gpmpc_safe
                           const double *x0, const double *U_nom, double *X, double *U, double *margin, int *flags,
                           int *iters);
 
+/* ---- tube MPC: uncertainty tubes ---------------------------------
+ * TubePropagator of the reference's src/safety/tube_mpc.py for the 14-state rocket (rocket: the
+ * 17 doubles of gpmpc_uprop6_linear), batch trajectories per call, host buffers, one upload,
+ * one device call, one read-back.  X_nom (batch x (N+1) x 14), U_nom (batch x N x 3), tubes
+ * (batch x (N+1) x 14) with tubes[b, 0] = 0.
+ * gpmpc_tube_linear: per (b, k) the forward-difference linearisation of the plant step at
+ * (X_nom[b,k], U_nom[b,k]) (the nominal step, x[i] += eps for the 14 states, u[i] += eps for
+ * the 3 controls, the differences divided by eps), A_cl = A + B K (A when K is NULL) and
+ * e_(k+1) = |A_cl| e_k + w_k.  w_mode 0: w_k = w_max on every row (w unused); 1: w holds 14
+ * bounds; 2: w is (batch x N x 14).  A_out (batch x N x 14 x 14) and B_out (batch x N x 14 x 3)
+ * receive the linearisation when not NULL.
+ * gpmpc_tube_mc: n_samples particles per trajectory from X_nom[b, 0]; per step the plant step
+ * plus noise[b, k, i, :] (batch x N x n_samples x 14, the caller's draws already times w_max);
+ * tubes[b, k+1, d] = numpy's linear-method quantile of |x - X_nom[b, k+1]| over the particles
+ * (virtual index (n - 1) q, _lerp with its t >= 0.5 form); NaN where a deviation is NaN.
+ * gpmpc_tube_plan (no device): k_tile = the horizon steps one pass of the linear kernel takes,
+ * mc_cap = the largest n_samples gpmpc_tube_mc accepts.
+ * -2 with gpmpc_last_error set for a null pointer, batch < 1, N < 1, dt not positive and
+ * finite, eps zero or not finite, a w_mode outside 0..2, a singular J_B, n_samples outside
+ * 1..mc_cap and a quantile outside [0, 1]; the context stays usable. */
+int gpmpc_tube_linear(gpmpc_ctx *ctx, const double *rocket, int batch, int N, double dt, double eps,
+                      const double *X_nom, const double *U_nom, const double *w, int w_mode, double w_max,
+                      const double *K, double *tubes, double *A_out, double *B_out);
+int gpmpc_tube_mc(gpmpc_ctx *ctx, const double *rocket, int batch, int N, int n_samples, double dt, double quantile,
+                  const double *X_nom, const double *U_nom, const double *noise, double *tubes);
+int gpmpc_tube_plan(int N, int n_samples, int *k_tile, int *mc_cap);
+
 #ifdef __cplusplus
 }
 #endif
