@@ -717,50 +717,10 @@ QP_STATUS_TEXT = {1: "solved", 2: "solved_inaccurate", -2: "maximum iterations r
                   -10: "unsolved", -100: "kkt factorisation failed"}
 
 
-def uprop3_linear(ctx, gp, X0, U, S0=None, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0), s0_diag=1e-6):
-    """gpmpc_uprop3_linear: the 3-DoF linear uncertainty propagation of B trajectories on the
-    device.  gp: an ExactGPHandle of the 3-DoF GP; X0 (B, 7), U (B, N, 3), S0 None or
-    (B, 7, 7) -> means (B, N+1, 7), covariances (B, N+1, 7, 7)."""
-    X0 = f64(np.atleast_2d(X0)); U = f64(U)
-    B, N = U.shape[0], U.shape[1]
-    if X0.shape != (B, 7) or U.shape != (B, N, 3):
-        raise ValueError(f"uprop3_linear: shapes X0 {X0.shape}, U {U.shape}")
-    g3 = f64(np.asarray(g, float).reshape(3))
-    means = np.empty((B, N + 1, 7)); covs = np.empty((B, N + 1, 7, 7))
-    s0 = None
-    if S0 is not None:
-        S0 = f64(S0)
-        if S0.shape != (B, 7, 7):
-            raise ValueError(f"uprop3_linear: S0 shape {S0.shape}")
-        s0 = S0.ctypes.data_as(_vp)
-    _chk(_L.gpmpc_uprop3_linear(ctx.h, gp.h, B, N, float(dt), float(alpha), _d(g3), _d(X0), _d(U), s0,
-                                float(s0_diag), _d(means), _d(covs)), "uprop3_linear")
-    return means, covs
-
-
-def uprop6_linear(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, s0_diag=1e-6):
-    """gpmpc_uprop6_linear: the 14-state linear uncertainty propagation of B trajectories on
-    the device.  hv, hw: the StructuredRocketGP's device pair (ExactGPHandle with exact=True,
-    else FITCHandle); rocket: 17 doubles (J_B row-major, r_T_B, g_I, alpha, g0); X0 (B, 14),
-    U (B, N, 3), S0 None or (B, 14, 14) -> means (B, N+1, 14), covariances (B, N+1, 14, 14)."""
-    X0 = f64(np.atleast_2d(X0)); U = f64(U)
-    B, N = U.shape[0], U.shape[1]
-    if X0.shape != (B, 14) or U.shape != (B, N, 3):
-        raise ValueError(f"uprop6_linear: shapes X0 {X0.shape}, U {U.shape}")
-    rk = f64(np.asarray(rocket, float).reshape(17))
-    means = np.empty((B, N + 1, 14)); covs = np.empty((B, N + 1, 14, 14))
-    s0 = None
-    if S0 is not None:
-        S0 = f64(S0)
-        if S0.shape != (B, 14, 14):
-            raise ValueError(f"uprop6_linear: S0 shape {S0.shape}")
-        s0 = S0.ctypes.data_as(_vp)
-    _chk(_L.gpmpc_uprop6_linear(ctx.h, hv.h, hw.h, int(bool(exact)), _d(rk), B, N, float(dt), _d(X0), _d(U), s0,
-                                float(s0_diag), _d(means), _d(covs)), "uprop6_linear")
-    return means, covs
-
-
-def _ut_buffers(what, nx, X0, U, S0, ut):
+def _uprop_buffers(what, nx, X0, U, S0):
+    """What every propagation wrapper takes and returns: X0 (B, nx), U (B, N, 3) and S0 (None
+    or (B, nx, nx)) as contiguous float64, their shapes checked; S0's pointer (or None); the
+    means (B, N+1, nx) and covariances (B, N+1, nx, nx) to fill."""
     X0 = f64(np.atleast_2d(X0)); U = f64(U)
     B, N = U.shape[0], U.shape[1]
     if X0.shape != (B, nx) or U.shape != (B, N, 3):
@@ -771,8 +731,36 @@ def _ut_buffers(what, nx, X0, U, S0, ut):
         if S0.shape != (B, nx, nx):
             raise ValueError(f"{what}: S0 shape {S0.shape}")
         s0 = S0.ctypes.data_as(_vp)
+    return X0, U, S0, s0, np.empty((B, N + 1, nx)), np.empty((B, N + 1, nx, nx))
+
+
+def uprop3_linear(ctx, gp, X0, U, S0=None, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0), s0_diag=1e-6):
+    """gpmpc_uprop3_linear: the 3-DoF linear uncertainty propagation of B trajectories on the
+    device.  gp: an ExactGPHandle of the 3-DoF GP; X0 (B, 7), U (B, N, 3), S0 None or
+    (B, 7, 7) -> means (B, N+1, 7), covariances (B, N+1, 7, 7)."""
+    X0, U, S0, s0, means, covs = _uprop_buffers("uprop3_linear", 7, X0, U, S0)
+    g3 = f64(np.asarray(g, float).reshape(3))
+    _chk(_L.gpmpc_uprop3_linear(ctx.h, gp.h, U.shape[0], U.shape[1], float(dt), float(alpha), _d(g3), _d(X0), _d(U), s0,
+                                float(s0_diag), _d(means), _d(covs)), "uprop3_linear")
+    return means, covs
+
+
+def uprop6_linear(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, s0_diag=1e-6):
+    """gpmpc_uprop6_linear: the 14-state linear uncertainty propagation of B trajectories on
+    the device.  hv, hw: the StructuredRocketGP's device pair (ExactGPHandle with exact=True,
+    else FITCHandle); rocket: 17 doubles (J_B row-major, r_T_B, g_I, alpha, g0); X0 (B, 14),
+    U (B, N, 3), S0 None or (B, 14, 14) -> means (B, N+1, 14), covariances (B, N+1, 14, 14)."""
+    X0, U, S0, s0, means, covs = _uprop_buffers("uprop6_linear", 14, X0, U, S0)
+    rk = f64(np.asarray(rocket, float).reshape(17))
+    _chk(_L.gpmpc_uprop6_linear(ctx.h, hv.h, hw.h, int(bool(exact)), _d(rk), U.shape[0], U.shape[1], float(dt), _d(X0), _d(U), s0,
+                                float(s0_diag), _d(means), _d(covs)), "uprop6_linear")
+    return means, covs
+
+
+def _ut_buffers(what, nx, X0, U, S0, ut):
+    X0, U, S0, s0, means, covs = _uprop_buffers(what, nx, X0, U, S0)
     ut3 = f64(np.asarray(ut, float).reshape(3))
-    return X0, U, S0, s0, ut3, np.empty((B, N + 1, nx)), np.empty((B, N + 1, nx, nx)), np.zeros(B, np.int32)
+    return X0, U, S0, s0, ut3, means, covs, np.zeros(U.shape[0], np.int32)
 
 
 def uprop3_unscented(ctx, gp, exact, X0, U, S0=None, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0),
@@ -804,25 +792,18 @@ def uprop6_unscented(ctx, hv, hw, exact, rocket, X0, U, S0=None, dt=0.1, ut=(1e-
 
 
 def _mc_buffers(what, nx, groups, X0, U, S0, particles0, normals, return_particles):
-    X0 = f64(np.atleast_2d(X0)); U = f64(U); particles0 = f64(particles0); normals = f64(normals)
+    U = f64(U); particles0 = f64(particles0); normals = f64(normals)
     if U.ndim != 3 or particles0.ndim != 3:
         raise ValueError(f"{what}: shapes U {U.shape}, particles0 {particles0.shape}")
+    X0, U, S0, s0, means, covs = _uprop_buffers(what, nx, X0, U, S0)
     B, N, S = U.shape[0], U.shape[1], particles0.shape[1]
-    if X0.shape != (B, nx) or U.shape != (B, N, 3):
-        raise ValueError(f"{what}: shapes X0 {X0.shape}, U {U.shape}")
     if particles0.shape != (B, S, nx):
         raise ValueError(f"{what}: particles0 shape {particles0.shape}, expected {(B, S, nx)}")
     if normals.shape != (B, N, S, groups, 3):
         raise ValueError(f"{what}: normals shape {normals.shape}, expected {(B, N, S, groups, 3)}")
-    s0 = None
-    if S0 is not None:
-        S0 = f64(S0)
-        if S0.shape != (B, nx, nx):
-            raise ValueError(f"{what}: S0 shape {S0.shape}")
-        s0 = S0.ctypes.data_as(_vp)
     paths = np.empty((B, N + 1, S, nx)) if return_particles else None
     pp = None if paths is None else paths.ctypes.data_as(_vp)
-    return X0, U, S0, s0, particles0, normals, np.empty((B, N + 1, nx)), np.empty((B, N + 1, nx, nx)), paths, pp
+    return X0, U, S0, s0, particles0, normals, means, covs, paths, pp
 
 
 def uprop3_mc(ctx, gp, exact, X0, U, S0, particles0, normals, dt=0.1, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0),

@@ -53,9 +53,11 @@ struct R6Rocket {
   int full;
 };
 
-// R6Rocket from the 17 doubles of gpmpc_uprop6_linear's packing (uprop_ut.hip); what: the
-// caller's name in the error message.  0, or -2 with the error set.
-int ut_rocket(const double *rocket, R6Rocket &rk, const char *what);
+// R6Rocket from the 17 doubles of gpmpc_uprop6_linear's packing (fleet6.hip, beside the
+// rollout's own inertia set-up: a diagonal J_B runs as its diagonal, any other as J and
+// J^-1); what: the caller's name in the error message.  0, or -2 with the error set.  Jf
+// and Ji of a diagonal tensor are left as the caller initialised them (zero).
+int r6_rocket(const double *rocket, R6Rocket &rk, const char *what);
 
 __device__ __forceinline__ void r6_mat3(const double *M, const double *v, double *o) {
   for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * v[0] + M[3 * i + 1] * v[1]) + M[3 * i + 2] * v[2];

@@ -291,7 +291,7 @@ static int sf_check(const char *what, const double *rocket, const gpmpc_safety_c
     gpmpc_set_error("%s: n_iters must not be negative", what);
     return -2;
   }
-  if (ut_rocket(rocket, a.rk, what)) return -2;
+  if (r6_rocket(rocket, a.rk, what)) return -2;
   a.horizon = cfg->horizon;
   a.n_iters = cfg->n_iters;
   a.have_constraints = cfg->have_constraints;

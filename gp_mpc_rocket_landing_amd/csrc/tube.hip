@@ -208,7 +208,7 @@ extern "C" int gpmpc_tube_linear(gpmpc_ctx *ctx, const double *rocket, int batch
     return -2;
   }
   TbArgs a{};
-  if (ut_rocket(rocket, a.rk, "tube_linear")) return -2;
+  if (r6_rocket(rocket, a.rk, "tube_linear")) return -2;
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t B = batch, BN = B * (size_t)N, nw = w_mode == 0 ? 0 : w_mode == 1 ? R6_NX : BN * R6_NX;
@@ -255,7 +255,7 @@ extern "C" int gpmpc_tube_mc(gpmpc_ctx *ctx, const double *rocket, int batch, in
     return -2;
   }
   TmArgs a{};
-  if (ut_rocket(rocket, a.rk, "tube_mc")) return -2;
+  if (r6_rocket(rocket, a.rk, "tube_mc")) return -2;
   // numpy's linear method: the virtual index (n - 1) q, its floor and the next index, both the
   // last index at or past n - 1 (where numpy's previous index is -1, so gamma = v + 1)
   const double v = (double)(n_samples - 1) * quantile;

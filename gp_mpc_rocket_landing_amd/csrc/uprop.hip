@@ -17,8 +17,12 @@
 // For the 3-DoF model the whole recursion runs on the device (gpmpc_uprop3_linear, below):
 // k_uprop3_means walks each trajectory's means with the exact GP mean at every step and
 // writes the A_k, the GP's batched posterior gives the variances, k_uprop3_q turns them
-// into the q_k, and k_cov_propagate does the rest.
-#include "internal.h"
+// into the q_k, and k_cov_propagate does the rest.  The 14-state model over a
+// StructuredRocketGP pair does the same with k_uprop6_means / k_uprop6_q
+// (gpmpc_uprop6_linear, at the end).  What these kernels share with the unscented and
+// Monte-Carlo propagators is in uprop.h.
+#include "uprop.h"
+#include "fleet6.h"
 
 #define UP_NXMAX 16
 
@@ -146,34 +150,17 @@ extern "C" int gpmpc_cov_propagate(gpmpc_ctx *ctx, int batch, int N, int nx, con
 #define NX 7      // the 3-DoF model's sizes (features3, internal.h): state, control,
 #define NU 3      // GP features
 #define NFEAT 11
-#define UP3_R 4  // training rows per thread held in registers (n <= 1024); larger n reads them per step
-#define UP_NCAP 256  // horizon steps whose controls the propagation kernels stage in LDS
 __global__ __launch_bounds__(256) void k_uprop3_means(GpView g, int N, double dt, double alpha, double g0,
                                                       double g1, double g2, const double *__restrict__ x0,
                                                       const double *__restrict__ U, double *__restrict__ Q,
                                                       double *__restrict__ A, double *__restrict__ means) {
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   __shared__ double sx[NX], sz[NFEAT], szn, red[4][3];
-  // this thread's training rows j = tid + 256 r (scaled features, |x_j|^2, alpha), loaded once:
-  // the N sequential steps then read no global memory on their critical path
-  const bool reg = g.n <= 256 * UP3_R;
-  double xr[UP3_R][NFEAT], xnr[UP3_R], ar[UP3_R][3];
-#pragma unroll
-  for (int r = 0; r < UP3_R; ++r) {
-    const int j = tid + 256 * r;
-    const bool ok = reg && j < g.n;
-#pragma unroll
-    for (int f = 0; f < NFEAT; ++f) xr[r][f] = ok ? g.Xs[(int64_t)j * NFEAT + f] : 0.0;
-    xnr[r] = ok ? g.Xn[j] : 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ar[r][c] = ok ? g.alphaT[(int64_t)c * g.n + j] : 0.0;
-  }
-  // the trajectory's controls staged in LDS once (up to UP_NCAP steps): no global
-  // round trip on the step chain
   __shared__ double sU[UP_NCAP * NU];
-  const bool uc = N <= UP_NCAP;
-  for (int e = tid; uc && e < N * NU; e += 256) sU[e] = U[(int64_t)b * N * NU + e];
-  const double *Ub = uc ? sU : U + (int64_t)b * N * NU;
+  const bool reg = g.n <= 256 * UP_R3;
+  GpRows<NFEAT, UP_R3> rows;
+  gp_rows_load(g, reg, rows);
+  const double *Ub = up_controls(U, b, N, sU);
   if (tid < NX) {
     sx[tid] = x0[(int64_t)b * NX + tid];
     means[(int64_t)b * (N + 1) * NX + tid] = sx[tid];
@@ -183,15 +170,8 @@ __global__ __launch_bounds__(256) void k_uprop3_means(GpView g, int N, double dt
     const double *u = Ub + k * NU;
     if (tid == 0) {
       double z[NFEAT];
-      features3(sx, u, z);
-      double sn = 0.0;
-      for (int f = 0; f < NFEAT; ++f) {
-        Q[((int64_t)b * N + k) * NFEAT + f] = z[f];
-        const double v = g.kind == GPMPC_SE_ISO ? z[f] : z[f] / g.ls[f];
-        sz[f] = v;
-        sn += v * v;
-      }
-      szn = sn;
+      szn = up3_query_row(g, sx, u, z, sz);
+      for (int f = 0; f < NFEAT; ++f) Q[((int64_t)b * N + k) * NFEAT + f] = z[f];
     } else if (tid >= 64 && tid < 64 + NX * NX) {
       // A_k = I + dt J: J[1:4, 4:7] = I, J[4:7, 0] = -u / m^2 (rocket_3dof.py jacobian_x), one entry a thread
       const int e = tid - 64, r = e / NX, c = e - r * NX;
@@ -201,38 +181,7 @@ __global__ __launch_bounds__(256) void k_uprop3_means(GpView g, int N, double dt
       A[((int64_t)b * N + k) * NX * NX + e] = v;
     }
     __syncthreads();
-    double acc[3] = {0.0, 0.0, 0.0};
-    const double zn = szn;
-    if (reg) {
-      double zv[NFEAT];
-#pragma unroll
-      for (int f = 0; f < NFEAT; ++f) zv[f] = sz[f];
-#pragma unroll
-      for (int r = 0; r < UP3_R; ++r) {
-        if (tid + 256 * r >= g.n) break;
-        double dot = 0.0;
-#pragma unroll
-        for (int f = 0; f < NFEAT; ++f) dot = fma(zv[f], xr[r][f], dot);
-        const double kv = kernel_epilogue(g.kind, (zn + xnr[r]) - 2.0 * dot, g.sigma2, g.iso_scale);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = fma(kv, ar[r][c], acc[c]);
-      }
-    } else {
-      for (int j = tid; j < g.n; j += 256) {
-        double dot = 0.0;
-#pragma unroll
-        for (int f = 0; f < NFEAT; ++f) dot = fma(sz[f], g.Xs[(int64_t)j * NFEAT + f], dot);
-        const double kv = kernel_epilogue(g.kind, (zn + g.Xn[j]) - 2.0 * dot, g.sigma2, g.iso_scale);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = fma(kv, g.alphaT[(int64_t)c * g.n + j], acc[c]);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
-    if (lane == 0)
-      for (int c = 0; c < 3; ++c) red[wave][c] = acc[c];
+    gp_rows_means<NFEAT, UP_R3, 1, 1, 3>(g, reg, rows, sz, &szn, &red[0][0], 3, 0);
     __syncthreads();
     if (tid == 0) {
       double dv[3];
@@ -241,13 +190,9 @@ __global__ __launch_bounds__(256) void k_uprop3_means(GpView g, int N, double dt
         dv[c] = __dadd_rn(__dmul_rn(m, g.ystd[c]), g.ymean[c]);
       }
       // x + dt f(x, u), then + d_v dt on the velocity rows
-      const double um = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(u[0], u[0]), __dmul_rn(u[1], u[1])), __dmul_rn(u[2], u[2])));
-      double f[NX];
-      f[0] = __dmul_rn(-alpha, um);
-      f[1] = sx[4]; f[2] = sx[5]; f[3] = sx[6];
-      f[4] = __dadd_rn(u[0] / sx[0], g0); f[5] = __dadd_rn(u[1] / sx[0], g1); f[6] = __dadd_rn(u[2] / sx[0], g2);
+      const double g3[3] = {g0, g1, g2};
       double xn[NX];
-      for (int i = 0; i < NX; ++i) xn[i] = __dadd_rn(sx[i], __dmul_rn(dt, f[i]));
+      up3_euler(sx, u, alpha, g3, dt, xn);
       for (int c = 0; c < 3; ++c) xn[4 + c] = __dadd_rn(xn[4 + c], __dmul_rn(dv[c], dt));
       for (int i = 0; i < NX; ++i) {
         sx[i] = xn[i];
@@ -269,11 +214,8 @@ extern "C" int gpmpc_uprop3_linear(gpmpc_ctx *ctx, gpmpc_gp *gp, int batch, int 
                                    const double *g3, const double *x0, const double *U, const double *S0,
                                    double s0_diag, double *means, double *covs) {
   GPMPC_CHECK_ARG(ctx && gp && g3 && x0 && U && means && covs && batch >= 0 && N >= 0);
-  const GpView g = gp_view(gp);
-  if (g.d != NFEAT || g.n_out != 3 || g.kind == GPMPC_KPROG) {
-    gpmpc_set_error("uprop3_linear: needs the 3-DoF exact GP (11 features, 3 outputs, a leaf kernel)");
-    return -2;
-  }
+  GpView g;
+  if (up_view3(gp, 1, "uprop3_linear", "exact GP", g)) return -2;
   if (batch == 0) return 0;
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -283,30 +225,174 @@ extern "C" int gpmpc_uprop3_linear(gpmpc_ctx *ctx, gpmpc_gp *gp, int batch, int 
   GPMPC_HIP(dA.alloc(s, sizeof(double) * (P * NX * NX + 1)));
   GPMPC_HIP(dq.alloc(s, sizeof(double) * (P * NX + 1)));
   // inputs in one pinned upload, means and covariances in one read-back
-  const size_t bytes = Stage::pad(8 * B * NX) + Stage::pad(8 * P * NU) + (S0 ? Stage::pad(8 * B * NX * NX) : 0) +
-                       Stage::pad(8 * B * (N + 1) * NX) + Stage::pad(8 * B * (N + 1) * NX * NX);
-  Stage sg(s, bytes);
+  Stage sg(s, UpIo::bytes(B, N, NX, S0));
   if (!sg.ok()) {
     gpmpc_set_error("uprop3_linear: staging buffers: out of memory");
     return -1;
   }
-  const double *dx0 = sg.in(x0, B * NX), *dU = sg.in(U, P * NU);
-  const double *dS0 = S0 ? sg.in(S0, B * NX * NX) : nullptr;
-  double *dmeans = sg.out(means, B * (N + 1) * NX), *dcov = sg.out(covs, B * (N + 1) * NX * NX);
+  const UpIo io(sg, B, N, NX, x0, U, S0, means, covs);
   GPMPC_HIP(sg.upload());
-  hipLaunchKernelGGL(k_uprop3_means, dim3(batch), dim3(256), 0, s, g, N, dt, alpha, g3[0], g3[1], g3[2], dx0, dU,
-                     dQ.as<double>(), dA.as<double>(), dmeans);
+  hipLaunchKernelGGL(k_uprop3_means, dim3(batch), dim3(256), 0, s, g, N, dt, alpha, g3[0], g3[1], g3[2], io.x0, io.U,
+                     dQ.as<double>(), dA.as<double>(), io.means);
   GPMPC_HIP(hipGetLastError());
   if (P) {
     GPMPC_HIP(dmu.alloc(s, sizeof(double) * P * 3));
     GPMPC_HIP(dvar.alloc(s, sizeof(double) * P * 3));
-    const int rc = gp_posterior_dev(ctx, gp, dQ.as<double>(), (int)P, dmu.as<double>(), dvar.as<double>());
+    const int rc = up_posterior(ctx, gp, 1, NFEAT, dQ.as<double>(), P, dmu.as<double>(), dvar.as<double>(), P);
     if (rc) return rc;
     hipLaunchKernelGGL(k_uprop3_q, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (int)P, dt * dt,
                        dvar.as<double>(), dq.as<double>());
     GPMPC_HIP(hipGetLastError());
   }
-  const int rc = gpmpc_cov_propagate_dev(ctx, batch, N, NX, dA.as<double>(), dq.as<double>(), dS0, s0_diag, dcov);
+  const int rc = gpmpc_cov_propagate_dev(ctx, batch, N, NX, dA.as<double>(), dq.as<double>(), io.S0, s0_diag, io.covs);
+  if (rc) return rc;
+  GPMPC_HIP(sg.download());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// UncertaintyPropagator._propagate_linear (uncertainty_prop.py:117-177) for the 14-state
+// model over a StructuredRocketGP pair, batch trajectories at once (gpmpc_uprop6_linear).
+// One workgroup per trajectory walks the N steps: the raw features of (x_k, u_k) (six
+// roles on six lanes, r6_features_role with unit length-scales) and -[A_d | B_d] at
+// (x_k, u_k) (r6_neg_lin, one lane of wave 1) side by side; then the features scaled by
+// each GP's length-scales (the k_scale_rows arithmetic), both GPs' means over their rows
+// (all threads, a fixed-order reduction), and on thread 0 the RK4 step with quaternion
+// normalisation (rocket_6dof.py step) plus dt d_v / dt d_w on the velocity / rate rows.
+// The variances of all B N queries then come from each GP's batched posterior, and one
+// launch propagates every covariance (k_cov_propagate).
+__global__ __launch_bounds__(256) void k_uprop6_means(GpView gv, GpView gw, R6Rocket rk, int N, double dt,
+                                                      const double *__restrict__ x0, const double *__restrict__ U,
+                                                      double *__restrict__ Qv, double *__restrict__ Qw,
+                                                      double *__restrict__ A, double *__restrict__ means) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  __shared__ double sx[R6_NX], sxn[R6_NX], qv[13], qw[12], zv[13], zw[12], red[4][6];
+  __shared__ double blk[R6_NX * R6_SZ];
+  __shared__ double sU[UP_NCAP * R6_NU];
+  // this thread's row of each GP (row tid), held in registers for the N steps when both
+  // GPs have at most 256 rows (FITC inducing sets); else read per step
+  const bool reg = gv.n <= 256 && gw.n <= 256;
+  GpRows<13, 1> rv;
+  GpRows<12, 1> rw;
+  gp_rows_load(gv, reg, rv);
+  gp_rows_load(gw, reg, rw);
+  const double *Ub = up_controls(U, b, N, sU);
+  if (tid < R6_NX) {
+    sx[tid] = x0[(int64_t)b * R6_NX + tid];
+    means[(int64_t)b * (N + 1) * R6_NX + tid] = sx[tid];
+  }
+  __syncthreads();
+  for (int k = 0; k < N; ++k) {
+    const int64_t pk = (int64_t)b * N + k;
+    const double *su = Ub + k * R6_NU;
+    // the raw features (six roles, six lanes), -[A_d | B_d] and the nominal RK4 step, side by side
+    if (tid < R6_FEAT_ROLES) {
+      const double one[13] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+      r6_features_role(tid, sx, su, one, one, qv, qw);
+    } else if (tid == 64) {
+      for (int e = 0; e < R6_NX * R6_SZ; ++e) blk[e] = 0.0;
+      r6_neg_lin(rk, sx, su, dt, blk);
+    } else if (tid == 255) {
+      r6_step(rk, sx, su, dt, sxn);
+    }
+    __syncthreads();
+    if (tid < 13) {
+      zv[tid] = gv.kind == GPMPC_SE_ISO ? qv[tid] : qv[tid] / gv.ls[tid];
+      Qv[pk * 13 + tid] = qv[tid];
+    } else if (tid >= 64 && tid < 76) {
+      const int f = tid - 64;
+      zw[f] = gw.kind == GPMPC_SE_ISO ? qw[f] : qw[f] / gw.ls[f];
+      Qw[pk * 12 + f] = qw[f];
+    } else if (tid >= 128 && tid < 128 + 98) {  // A_k = I + A_c dt = -(the block's first 14 columns)
+      for (int e = tid - 128; e < R6_NX * R6_NX; e += 98) {
+        const int r = e / R6_NX, c = e - r * R6_NX;
+        A[pk * R6_NX * R6_NX + e] = -blk[r * R6_SZ + c];
+      }
+    }
+    __syncthreads();
+    double znv = 0.0, znw = 0.0;  // every thread forms the two squared norms itself
+#pragma unroll
+    for (int f = 0; f < 13; ++f) znv += zv[f] * zv[f];
+#pragma unroll
+    for (int f = 0; f < 12; ++f) znw += zw[f] * zw[f];
+    gp_rows_means<13, 1, 1, 1, 6>(gv, reg, rv, zv, &znv, &red[0][0], 6, 0);
+    gp_rows_means<12, 1, 1, 1, 6>(gw, reg, rw, zw, &znw, &red[0][0], 6, 3);
+    __syncthreads();
+    if (tid == 0) {
+      double d[6];
+      for (int c = 0; c < 6; ++c) {
+        const double m = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+        const GpView &g = c < 3 ? gv : gw;
+        d[c] = m * g.ystd[c % 3] + g.ymean[c % 3];
+      }
+      double xn[R6_NX];
+      for (int i = 0; i < R6_NX; ++i) xn[i] = sxn[i];
+      for (int c = 0; c < 3; ++c) {
+        xn[4 + c] = xn[4 + c] + d[c] * dt;
+        xn[11 + c] = xn[11 + c] + d[3 + c] * dt;
+      }
+      for (int i = 0; i < R6_NX; ++i) {
+        sx[i] = xn[i];
+        means[((int64_t)b * (N + 1) + k + 1) * R6_NX + i] = xn[i];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// q_k = var dt^2 on the velocity rows 4-6 (d_v) and the rate rows 11-13 (d_omega)
+__global__ void k_uprop6_q(int P, double dt2, const double *__restrict__ vv, const double *__restrict__ vw,
+                           double *__restrict__ q) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= P) return;
+  for (int i = 0; i < R6_NX; ++i) {
+    double v = 0.0;
+    if (i >= 4 && i < 7) v = vv[(int64_t)j * 3 + i - 4] * dt2;
+    if (i >= 11) v = vw[(int64_t)j * 3 + i - 11] * dt2;
+    q[(int64_t)j * R6_NX + i] = v;
+  }
+}
+
+extern "C" int gpmpc_uprop6_linear(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact, const double *rocket,
+                                   int batch, int N, double dt, const double *x0, const double *U,
+                                   const double *S0, double s0_diag, double *means, double *covs) {
+  GPMPC_CHECK_ARG(ctx && gp_v && gp_w && rocket && x0 && U && means && covs && batch >= 0 && N >= 0);
+  GpView gv, gw;
+  if (up_view6(gp_v, gp_w, exact, "uprop6_linear", gv, gw)) return -2;
+  R6Rocket rk{};
+  if (r6_rocket(rocket, rk, "uprop6_linear")) return -2;
+  if (batch == 0) return 0;
+  GPMPC_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t B = batch, P = B * N;
+  DevBuf dQv, dQw, dA, dq, mv, vv, mw, vw;
+  GPMPC_HIP(dQv.alloc(s, sizeof(double) * (P * 13 + 1)));
+  GPMPC_HIP(dQw.alloc(s, sizeof(double) * (P * 12 + 1)));
+  GPMPC_HIP(dA.alloc(s, sizeof(double) * (P * R6_NX * R6_NX + 1)));
+  GPMPC_HIP(dq.alloc(s, sizeof(double) * (P * R6_NX + 1)));
+  // inputs in one pinned upload, means and covariances in one read-back
+  Stage sg(s, UpIo::bytes(B, N, R6_NX, S0));
+  if (!sg.ok()) {
+    gpmpc_set_error("uprop6_linear: staging buffers: out of memory");
+    return -1;
+  }
+  const UpIo io(sg, B, N, R6_NX, x0, U, S0, means, covs);
+  GPMPC_HIP(sg.upload());
+  hipLaunchKernelGGL(k_uprop6_means, dim3(batch), dim3(256), 0, s, gv, gw, rk, N, dt, io.x0, io.U, dQv.as<double>(),
+                     dQw.as<double>(), dA.as<double>(), io.means);
+  GPMPC_HIP(hipGetLastError());
+  if (P) {
+    for (DevBuf *d : {&mv, &vv, &mw, &vw}) GPMPC_HIP(d->alloc(s, sizeof(double) * P * 3));
+    int rc = up_posterior(ctx, gp_v, exact, 13, dQv.as<double>(), P, mv.as<double>(), vv.as<double>(), P);
+    if (rc) return rc;
+    rc = up_posterior(ctx, gp_w, exact, 12, dQw.as<double>(), P, mw.as<double>(), vw.as<double>(), P);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_uprop6_q, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (int)P, dt * dt,
+                       vv.as<double>(), vw.as<double>(), dq.as<double>());
+    GPMPC_HIP(hipGetLastError());
+  }
+  const int rc = gpmpc_cov_propagate_dev(ctx, batch, N, R6_NX, dA.as<double>(), dq.as<double>(), io.S0, s0_diag,
+                                         io.covs);
   if (rc) return rc;
   GPMPC_HIP(sg.download());
   return 0;

@@ -21,6 +21,7 @@
 // The draws (particles0, the standard normals) are the caller's: numpy's global RNG in the
 // reference's order, so a seed means what it means there.  The only synchronisation is the
 // final read-back.
+#include "uprop.h"
 #include "fleet6.h"
 #include <algorithm>
 #include <climits>
@@ -71,15 +72,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_step(McArgs a, int k) {
 #pragma unroll
     for (int r = 0; r < n; ++r) xc[r] = xp[r];
     if (MODEL == 3) {
-#pragma clang fp contract(off)
-      // x + dt f(x, u), f = [-alpha |u|, v, u / m + g]: products and sums unfused, as numpy forms them
-      const double um = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(u[0], u[0]), __dmul_rn(u[1], u[1])), __dmul_rn(u[2], u[2])));
-      double f[7];
-      f[0] = __dmul_rn(-a.alpha, um);
-      f[1] = xc[4]; f[2] = xc[5]; f[3] = xc[6];
-      f[4] = __dadd_rn(u[0] / xc[0], a.g3[0]); f[5] = __dadd_rn(u[1] / xc[0], a.g3[1]); f[6] = __dadd_rn(u[2] / xc[0], a.g3[2]);
-#pragma unroll
-      for (int r = 0; r < 7; ++r) x[r] = __dadd_rn(xc[r], __dmul_rn(dt, f[r]));
+      up3_euler(xc, u, a.alpha, a.g3, dt, x);
     } else {
       r6_step(a.rk, xc, u, dt, x);
     }
@@ -170,18 +163,6 @@ __global__ __launch_bounds__(MC_ST) void k_mc_stats(int N, int S, const double *
   }
 }
 
-// the posterior of P device-resident raw query rows, MC_PCHUNK rows a call
-static int mc_posterior(gpmpc_ctx *ctx, void *gp, int exact, int d, const double *dq, size_t P, double *dmean,
-                        double *dvar) {
-  for (size_t c0 = 0; c0 < P; c0 += MC_PCHUNK) {
-    const int pc = (int)std::min<size_t>(MC_PCHUNK, P - c0);
-    const int rc = exact ? gp_posterior_dev(ctx, (gpmpc_gp *)gp, dq + c0 * d, pc, dmean + c0 * 3, dvar + c0 * 3)
-                         : fitc_posterior_dev(ctx, (gpmpc_fitc *)gp, dq + c0 * d, pc, dmean + c0 * 3, dvar + c0 * 3);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
 template <int MODEL>
 static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void *gp_w, int exact, int batch, int N,
                   int n_samples, const double *x0, const double *U, const double *S0, double s0_diag,
@@ -198,9 +179,8 @@ static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void 
   hipStream_t s = ctx->stream;
   // inputs in one pinned upload; means, covariances (and the paths, when asked for) in one read-back
   const size_t npath = B * NP * S * n;
-  const size_t bytes = Stage::pad(8 * B * n) + Stage::pad(8 * B * N * 3) + (S0 ? Stage::pad(8 * B * n * n) : 0) +
-                       Stage::pad(8 * P * n) + Stage::pad(8 * B * N * S * G * 3) + Stage::pad(8 * B * NP * n) +
-                       Stage::pad(8 * B * NP * n * n) + (particles ? Stage::pad(8 * npath) : 0);
+  const size_t bytes = UpIo::bytes(B, N, n, S0) + Stage::pad(8 * P * n) + Stage::pad(8 * B * N * S * G * 3) +
+                       (particles ? Stage::pad(8 * npath) : 0);
   Stage sg(s, bytes);
   if (!sg.ok()) {
     gpmpc_set_error("%s: staging buffers: out of memory", what);
@@ -214,12 +194,10 @@ static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void 
     for (DevBuf *d : {&mw, &vw}) GPMPC_HIP(d->alloc(s, sizeof(double) * P * 3));
   }
   if (!particles) GPMPC_HIP(paths.alloc(s, sizeof(double) * npath));
-  const double *dx0 = sg.in(x0, B * n);
-  a.U = sg.in(U, B * N * 3);
-  const double *dS0 = S0 ? sg.in(S0, B * n * n) : nullptr;
   a.particles0 = sg.in(particles0, P * n);
   a.normals = sg.in(normals, B * N * S * G * 3);
-  double *dmeans = sg.out(means, B * NP * n), *dcovs = sg.out(covs, B * NP * n * n);
+  const UpIo io(sg, B, N, n, x0, U, S0, means, covs);
+  a.U = io.U;
   a.paths = particles ? sg.out(particles, npath) : paths.as<double>();
   a.B = batch; a.N = N; a.S = n_samples;
   a.Qv = dQv.as<double>(); a.Qw = dQw.as<double>();
@@ -228,16 +206,17 @@ static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void 
   const dim3 grid((unsigned)((P + MC_T - 1) / MC_T));
   for (int k = -1; k < N; ++k) {
     if (k >= 0) {
-      int rc = mc_posterior(ctx, gp_v, exact, DV, dQv.as<double>(), P, mv.as<double>(), vv.as<double>());
+      int rc = up_posterior(ctx, gp_v, exact, DV, dQv.as<double>(), P, mv.as<double>(), vv.as<double>(), MC_PCHUNK);
       if (rc) return rc;
-      if (MODEL == 6) rc = mc_posterior(ctx, gp_w, exact, DW, dQw.as<double>(), P, mw.as<double>(), vw.as<double>());
+      if (MODEL == 6)
+        rc = up_posterior(ctx, gp_w, exact, DW, dQw.as<double>(), P, mw.as<double>(), vw.as<double>(), MC_PCHUNK);
       if (rc) return rc;
     }
     hipLaunchKernelGGL(k_mc_step<MODEL>, grid, dim3(MC_T), 0, s, a, k);
     GPMPC_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_mc_stats<(int)n>, dim3((unsigned)(B * NP)), dim3(MC_ST), 0, s, N, n_samples, dx0, dS0, s0_diag,
-                     a.paths, dmeans, dcovs);
+  hipLaunchKernelGGL(k_mc_stats<(int)n>, dim3((unsigned)(B * NP)), dim3(MC_ST), 0, s, N, n_samples, io.x0, io.S0,
+                     s0_diag, a.paths, io.means, io.covs);
   GPMPC_HIP(hipGetLastError());
   GPMPC_HIP(sg.download());
   return 0;
@@ -249,11 +228,8 @@ extern "C" int gpmpc_uprop3_mc(gpmpc_ctx *ctx, void *gp, int exact, int batch, i
                                double *covs, double *particles) {
   GPMPC_CHECK_ARG(ctx && gp && g3 && x0 && U && particles0 && normals && means && covs && batch >= 0 && N >= 0 &&
                   n_samples >= 2);
-  const GpView g = exact ? gp_view((gpmpc_gp *)gp) : fitc_view((gpmpc_fitc *)gp);
-  if (g.d != 11 || g.n_out != 3 || g.kind == GPMPC_KPROG) {
-    gpmpc_set_error("uprop3_mc: needs the 3-DoF GP (11 features, 3 outputs, a leaf kernel)");
-    return -2;
-  }
+  GpView g;
+  if (up_view3(gp, exact, "uprop3_mc", "GP", g)) return -2;
   McArgs a{};
   a.alpha = alpha;
   for (int i = 0; i < 3; ++i) a.g3[i] = g3[i];
@@ -268,15 +244,10 @@ extern "C" int gpmpc_uprop6_mc(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int exact
                                double *covs, double *particles) {
   GPMPC_CHECK_ARG(ctx && gp_v && gp_w && rocket && x0 && U && particles0 && normals && means && covs && batch >= 0 &&
                   N >= 0 && n_samples >= 2);
-  const GpView gv = exact ? gp_view((gpmpc_gp *)gp_v) : fitc_view((gpmpc_fitc *)gp_v);
-  const GpView gw = exact ? gp_view((gpmpc_gp *)gp_w) : fitc_view((gpmpc_fitc *)gp_w);
-  if (gv.d != 13 || gw.d != 12 || gv.n_out != 3 || gw.n_out != 3 || gv.kind == GPMPC_KPROG ||
-      gw.kind == GPMPC_KPROG) {
-    gpmpc_set_error("uprop6_mc: needs the StructuredRocketGP pair (13 / 12 features, 3 outputs, leaf kernels)");
-    return -2;
-  }
+  GpView gv, gw;
+  if (up_view6(gp_v, gp_w, exact, "uprop6_mc", gv, gw)) return -2;
   McArgs a{};
-  if (ut_rocket(rocket, a.rk, "uprop6_mc")) return -2;
+  if (r6_rocket(rocket, a.rk, "uprop6_mc")) return -2;
   a.dt = dt;
   return mc_run<6>(ctx, a, "uprop6_mc", gp_v, gp_w, exact, batch, N, n_samples, x0, U, S0, s0_diag, particles0,
                    normals, means, covs, particles);

@@ -25,12 +25,11 @@
 //      per entry.
 // A non-positive pivot in step k's factor ends that trajectory: info[b] = k + 1 and its
 // remaining rows are NaN; the other trajectories do not notice.
+#include "uprop.h"
 #include "fleet6.h"
 #include <algorithm>
 #include <cmath>
 
-#define UT_NCAP 256    // horizon steps whose controls the kernel stages in LDS
-#define UT_R3 4        // 3-DoF: training rows per thread held in registers (n <= 1024)
 #define UT_MAXROWS 4096  // k* in dynamic LDS: 8 B a row next to ~30 KB of static LDS
 
 struct UtArgs {
@@ -47,96 +46,9 @@ struct UtArgs {
   int *info;
 };
 
-// this thread's rows j = tid + 256 r of a GP: scaled features, squared norm, alpha
-template <int D, int R>
-struct UtRows {
-  double x[R][D], xn[R], a[R][3];
-};
-
-template <int D, int R>
-__device__ __forceinline__ void ut_rows_load(const GpView &g, bool reg, UtRows<D, R> &w) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int j = tid + 256 * r;
-    const bool ok = reg && j < g.n;
-#pragma unroll
-    for (int f = 0; f < D; ++f) w.x[r][f] = ok ? g.Xs[(int64_t)j * D + f] : 0.0;
-    w.xn[r] = ok ? g.Xn[j] : 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) w.a[r][c] = ok ? g.alphaT[(int64_t)c * g.n + j] : 0.0;
-  }
-}
-
-// the GP's latent means (alpha^T k*) at the P scaled query rows sz (P x D, squared norms
-// szn): per-wave partials into red[wave * ldr + p * G + c0 + c], C points a pass
-template <int D, int R, int P, int C, int G>
-__device__ __forceinline__ void ut_gp_means(const GpView &g, bool reg, const UtRows<D, R> &w,
-                                            const double *sz, const double *szn, double *red, int ldr,
-                                            int c0) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll 1
-  for (int p0 = 0; p0 < P; p0 += C) {
-    double acc[C][3];
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c][0] = acc[c][1] = acc[c][2] = 0.0;
-    if (reg) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        if (p0 + c >= P) continue;
-        double z[D];
-#pragma unroll
-        for (int f = 0; f < D; ++f) z[f] = sz[(p0 + c) * D + f];
-        const double zn = szn[p0 + c];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if (tid + 256 * r < g.n) {
-            double dot = 0.0;
-#pragma unroll
-            for (int f = 0; f < D; ++f) dot = fma(z[f], w.x[r][f], dot);
-            const double kv = kernel_epilogue(g.kind, (zn + w.xn[r]) - 2.0 * dot, g.sigma2, g.iso_scale);
-#pragma unroll
-            for (int o = 0; o < 3; ++o) acc[c][o] = fma(kv, w.a[r][o], acc[c][o]);
-          }
-        }
-      }
-    } else {
-      for (int j = tid; j < g.n; j += 256) {
-        double xr[D], ar[3];
-#pragma unroll
-        for (int f = 0; f < D; ++f) xr[f] = g.Xs[(int64_t)j * D + f];
-        const double xn = g.Xn[j];
-#pragma unroll
-        for (int o = 0; o < 3; ++o) ar[o] = g.alphaT[(int64_t)o * g.n + j];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          if (p0 + c >= P) continue;
-          double dot = 0.0;
-#pragma unroll
-          for (int f = 0; f < D; ++f) dot = fma(sz[(p0 + c) * D + f], xr[f], dot);
-          const double kv = kernel_epilogue(g.kind, (szn[p0 + c] + xn) - 2.0 * dot, g.sigma2, g.iso_scale);
-#pragma unroll
-          for (int o = 0; o < 3; ++o) acc[c][o] = fma(kv, ar[o], acc[c][o]);
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      if (p0 + c >= P) continue;
-#pragma unroll
-      for (int o = 0; o < 3; ++o) {
-        double v = acc[c][o];
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-        if (lane == 0) red[wave * ldr + (p0 + c) * G + c0 + o] = v;
-      }
-    }
-  }
-}
-
 // k* of the scaled query row z (LDS) against every row of the GP, into sk[0 .. g.n)
 template <int D, int R>
-__device__ __forceinline__ void ut_kstar(const GpView &g, bool reg, const UtRows<D, R> &w, const double *zq,
+__device__ __forceinline__ void ut_kstar(const GpView &g, bool reg, const GpRows<D, R> &w, const double *zq,
                                          double zn, double *sk) {
   const int tid = threadIdx.x;
   double z[D];
@@ -250,7 +162,7 @@ __device__ __forceinline__ void ut_sumsq(const double *__restrict__ W, int n, co
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
   constexpr int n = MODEL == 3 ? 7 : 14, P = 2 * n + 1, G = MODEL == 3 ? 3 : 6;
-  constexpr int DV = MODEL == 3 ? 11 : 13, DW = 12, R = MODEL == 3 ? UT_R3 : 1;
+  constexpr int DV = MODEL == 3 ? 11 : 13, DW = 12, R = MODEL == 3 ? UP_R3 : 1;
   constexpr int CV = 5;  // points per pass of the means
   constexpr int UT_T = 4;  // 32-column chunks a batch of the W pass
   const int b = blockIdx.x, tid = threadIdx.x, N = a.N;
@@ -259,17 +171,15 @@ __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
   __shared__ double sx[n], sxn[n], sS[n][n + 1], sL[n][n + 1], sp[P][n], spn[P][n];
   __shared__ double zv[P][DV], zw[P][DW], znv[P], znw[P];
   __shared__ double red[4][P * G], redw[4][4], svar[G];
-  __shared__ double sU[UT_NCAP * 3];
+  __shared__ double sU[UP_NCAP * 3];
   __shared__ int sfail;
   const GpView &gv = a.gv, &gw = a.gw;
-  const bool reg = MODEL == 3 ? gv.n <= 256 * UT_R3 : (gv.n <= 256 && gw.n <= 256);
-  UtRows<DV, R> rv;
-  UtRows<DW, 1> rw;  // (the 14-state model only)
-  ut_rows_load(gv, reg, rv);
-  if (MODEL == 6) ut_rows_load(gw, reg, rw);
-  const bool uc = N <= UT_NCAP;
-  for (int e = tid; uc && e < N * 3; e += 256) sU[e] = a.U[(int64_t)b * N * 3 + e];
-  const double *Ub = uc ? sU : a.U + (int64_t)b * N * 3;
+  const bool reg = MODEL == 3 ? gv.n <= 256 * UP_R3 : (gv.n <= 256 && gw.n <= 256);
+  GpRows<DV, R> rv;
+  GpRows<DW, 1> rw;  // (the 14-state model only)
+  gp_rows_load(gv, reg, rv);
+  if (MODEL == 6) gp_rows_load(gw, reg, rw);
+  const double *Ub = up_controls(a.U, b, N, sU);
   double *mb = a.means + (int64_t)b * (N + 1) * n, *cb = a.covs + (int64_t)b * (N + 1) * n * n;
   if (tid < n) {
     sx[tid] = a.x0[(int64_t)b * n + tid];
@@ -331,28 +241,11 @@ __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
     // 3. the nominal step and the features of every point, side by side
     if (MODEL == 3) {
       if (tid < P) {
-#pragma clang fp contract(off)
-        // x + dt f(x, u), f = [-alpha |u|, v, u / m + g]: products and sums unfused, as numpy forms them
-        const double *x = sp[tid];
-        const double um = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(u[0], u[0]), __dmul_rn(u[1], u[1])), __dmul_rn(u[2], u[2])));
-        double f[7];
-        f[0] = __dmul_rn(-a.alpha, um);
-        f[1] = x[4]; f[2] = x[5]; f[3] = x[6];
-        f[4] = __dadd_rn(u[0] / x[0], a.g3[0]); f[5] = __dadd_rn(u[1] / x[0], a.g3[1]); f[6] = __dadd_rn(u[2] / x[0], a.g3[2]);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) spn[tid][i] = __dadd_rn(x[i], __dmul_rn(dt, f[i]));
+        up3_euler(sp[tid], u, a.alpha, a.g3, dt, spn[tid]);
       } else if (tid >= 64 && tid < 64 + P) {
         const int p = tid - 64;
         double z[11];
-        features3(sp[p], u, z);
-        double sn = 0.0;
-#pragma unroll
-        for (int f = 0; f < 11; ++f) {
-          const double v = gv.kind == GPMPC_SE_ISO ? z[f] : z[f] / gv.ls[f];
-          zv[p][f] = v;
-          sn += v * v;
-        }
-        znv[p] = sn;
+        znv[p] = up3_query_row(gv, sp[p], u, z, zv[p]);
       }
       __syncthreads();
     } else {
@@ -384,8 +277,8 @@ __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
       __syncthreads();
     }
     // 4. the GP means at the P points; 5. k* of the centre, |W k*|^2 (and |W2 k*|^2)
-    ut_gp_means<DV, R, P, CV, G>(gv, reg, rv, &zv[0][0], znv, &red[0][0], P * G, 0);
-    if (MODEL == 6) ut_gp_means<DW, 1, P, CV, G>(gw, reg, rw, &zw[0][0], znw, &red[0][0], P * G, 3);
+    gp_rows_means<DV, R, P, CV, G>(gv, reg, rv, &zv[0][0], znv, &red[0][0], P * G, 0);
+    if (MODEL == 6) gp_rows_means<DW, 1, P, CV, G>(gw, reg, rw, &zw[0][0], znw, &red[0][0], P * G, 3);
     ut_kstar<DV, R>(gv, reg, rv, zv[0], znv[0], sk);
     __syncthreads();
     const int wave = tid >> 6;
@@ -452,46 +345,6 @@ __global__ __launch_bounds__(256) void k_uprop_ut(UtArgs a) {
   }
 }
 
-// R6Rocket from the packing of gpmpc_uprop6_linear: J_B (9, row-major), r_T_B (3), g_I (3),
-// alpha, g0.  A diagonal tensor runs as its diagonal, any other as J and J^-1 (adjugate /
-// determinant, the expressions of the rollout's own set-up).  0, or -2 with the error set
-// (what: the caller's name in the message).  Shared with uprop_mc.hip (fleet6.h).
-int ut_rocket(const double *rocket, R6Rocket &rk, const char *what) {
-  const double *Jf = rocket;
-  bool joff = false;
-  for (int i = 0; i < 9; ++i) joff = joff || (i % 4 != 0 && Jf[i] != 0.0);
-  for (int i = 0; i < 3; ++i) { rk.J[i] = Jf[4 * i]; rk.rT[i] = rocket[9 + i]; rk.gI[i] = rocket[12 + i]; }
-  rk.full = joff;
-  rk.alpha = rocket[15];
-  rk.g0 = rocket[16];
-  if (!joff) {
-    for (int i = 0; i < 3; ++i)
-      if (!(rk.J[i] > 0.0)) {
-        gpmpc_set_error("%s: the rocket's J_B diagonal must be positive", what);
-        return -2;
-      }
-    return 0;
-  }
-  const double c00 = Jf[4] * Jf[8] - Jf[5] * Jf[7], c01 = Jf[5] * Jf[6] - Jf[3] * Jf[8],
-               c02 = Jf[3] * Jf[7] - Jf[4] * Jf[6];
-  const double det = Jf[0] * c00 + Jf[1] * c01 + Jf[2] * c02;
-  bool fin = std::isfinite(det);
-  double scale = 0.0;
-  for (int i = 0; i < 9; ++i) {
-    fin = fin && std::isfinite(Jf[i]);
-    scale = std::max(scale, std::fabs(Jf[i]));
-  }
-  if (!fin || !(std::fabs(det) > 1e-14 * scale * scale * scale)) {
-    gpmpc_set_error("%s: the rocket's J_B must be finite and invertible", what);
-    return -2;
-  }
-  const double adj[9] = {c00, Jf[2] * Jf[7] - Jf[1] * Jf[8], Jf[1] * Jf[5] - Jf[2] * Jf[4],
-                         c01, Jf[0] * Jf[8] - Jf[2] * Jf[6], Jf[2] * Jf[3] - Jf[0] * Jf[5],
-                         c02, Jf[1] * Jf[6] - Jf[0] * Jf[7], Jf[0] * Jf[4] - Jf[1] * Jf[3]};
-  for (int i = 0; i < 9; ++i) { rk.Jf[i] = Jf[i]; rk.Ji[i] = adj[i] / det; }
-  return 0;
-}
-
 // the unscented transform's constants from (alpha, beta, kappa), uncertainty_prop.py:196-210
 static void ut_weights(const double *ut, int n, UtArgs &a) {
   const double lam = std::pow(ut[0], 2.0) * (n + ut[2]) - n;
@@ -513,20 +366,15 @@ static int ut_run(gpmpc_ctx *ctx, UtArgs &a, const char *what, int batch, int N,
   if (batch == 0) return 0;
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const size_t B = batch, Pn = B * N;
+  const size_t B = batch;
   // inputs in one pinned upload; means, covariances and info in one read-back
-  const size_t bytes = Stage::pad(8 * B * n) + Stage::pad(8 * Pn * 3) + (S0 ? Stage::pad(8 * B * n * n) : 0) +
-                       Stage::pad(8 * B * (N + 1) * n) + Stage::pad(8 * B * (N + 1) * n * n) + Stage::pad(4 * B);
-  Stage sg(s, bytes);
+  Stage sg(s, UpIo::bytes(B, N, n, S0) + Stage::pad(4 * B));
   if (!sg.ok()) {
     gpmpc_set_error("%s: staging buffers: out of memory", what);
     return -1;
   }
-  a.x0 = sg.in(x0, B * n);
-  a.U = sg.in(U, Pn * 3);
-  a.S0 = S0 ? sg.in(S0, B * n * n) : nullptr;
-  a.means = sg.out(means, B * (N + 1) * n);
-  a.covs = sg.out(covs, B * (N + 1) * n * n);
+  const UpIo io(sg, B, N, n, x0, U, S0, means, covs);
+  a.x0 = io.x0; a.U = io.U; a.S0 = io.S0; a.means = io.means; a.covs = io.covs;
   a.info = sg.out(info, B);
   GPMPC_HIP(sg.upload());
   hipLaunchKernelGGL(k_uprop_ut<MODEL>, dim3(batch), dim3(256), sizeof(double) * (size_t)rows, s, a);
@@ -540,13 +388,8 @@ extern "C" int gpmpc_uprop3_unscented(gpmpc_ctx *ctx, void *gp, int exact, int b
                                       const double *S0, double s0_diag, double *means, double *covs, int *info) {
   GPMPC_CHECK_ARG(ctx && gp && g3 && ut && x0 && U && means && covs && info && batch >= 0 && N >= 0);
   UtArgs a{};
-  a.gv = exact ? gp_view((gpmpc_gp *)gp) : fitc_view((gpmpc_fitc *)gp);
+  if (up_view3(gp, exact, "uprop3_unscented", "GP", a.gv, &a.W2v)) return -2;
   a.gw = a.gv;
-  if (a.gv.d != 11 || a.gv.n_out != 3 || a.gv.kind == GPMPC_KPROG) {
-    gpmpc_set_error("uprop3_unscented: needs the 3-DoF GP (11 features, 3 outputs, a leaf kernel)");
-    return -2;
-  }
-  a.W2v = exact ? nullptr : fitc_W2((gpmpc_fitc *)gp);
   a.alpha = alpha;
   for (int i = 0; i < 3; ++i) a.g3[i] = g3[i];
   ut_weights(ut, 7, a);
@@ -562,17 +405,8 @@ extern "C" int gpmpc_uprop6_unscented(gpmpc_ctx *ctx, void *gp_v, void *gp_w, in
                                       double *covs, int *info) {
   GPMPC_CHECK_ARG(ctx && gp_v && gp_w && rocket && ut && x0 && U && means && covs && info && batch >= 0 && N >= 0);
   UtArgs a{};
-  a.gv = exact ? gp_view((gpmpc_gp *)gp_v) : fitc_view((gpmpc_fitc *)gp_v);
-  a.gw = exact ? gp_view((gpmpc_gp *)gp_w) : fitc_view((gpmpc_fitc *)gp_w);
-  if (a.gv.d != 13 || a.gw.d != 12 || a.gv.n_out != 3 || a.gw.n_out != 3 || a.gv.kind == GPMPC_KPROG ||
-      a.gw.kind == GPMPC_KPROG) {
-    gpmpc_set_error("uprop6_unscented: needs the StructuredRocketGP pair (13 / 12 features, 3 outputs, leaf kernels)");
-    return -2;
-  }
-  a.W2v = exact ? nullptr : fitc_W2((gpmpc_fitc *)gp_v);
-  a.W2w = exact ? nullptr : fitc_W2((gpmpc_fitc *)gp_w);
-  // rocket: J_B (9, row-major), r_T_B (3), g_I (3), alpha, g0 (gpmpc_uprop6_linear's packing)
-  if (ut_rocket(rocket, a.rk, "uprop6_unscented")) return -2;
+  if (up_view6(gp_v, gp_w, exact, "uprop6_unscented", a.gv, a.gw, &a.W2v, &a.W2w)) return -2;
+  if (r6_rocket(rocket, a.rk, "uprop6_unscented")) return -2;
   ut_weights(ut, 14, a);
   a.N = N;
   a.dt = dt;

@@ -255,3 +255,125 @@ def test_propagate_batch_6dof_device_vs_host_loop(gpu_ctx, sparse, full_j, s0):
     np.testing.assert_array_equal(md[:, 0], X0)
     np.testing.assert_allclose(md, mh, rtol=1e-10, atol=1e-11)
     np.testing.assert_allclose(cd, ch, rtol=1e-7, atol=1e-15)
+
+
+# ---- what the three propagators share (csrc/uprop.h), at its edges ------------------------
+def _hover3(B, N, seed):
+    from gp_mpc_rocket_landing_amd.fleet import initial_conditions
+    X0 = initial_conditions(B)
+    rs = np.random.RandomState(seed)
+    return X0, np.tile((-X0[:, 0:1] * np.array([-1.0, 0, 0]))[:, None, :], (1, N, 1)) * (1 + 0.1 * rs.randn(B, N, 1))
+
+
+def _gp3_synthetic(n):
+    from gp_mpc_rocket_landing_amd.data import synthetic_training_data
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    X, U, D = synthetic_training_data(n, seed=1)
+    gp = Simple3DoFGP(use_sparse=False)
+    gp.add_data(X, U, D); gp.fit()
+    return gp
+
+
+def _hover6(B, N, seed):
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig
+    from gp_mpc_rocket_landing_amd.rollouts6 import initial_conditions_6dof
+    X0 = initial_conditions_6dof(B)
+    X0[:, 11:14] = np.array([0.02, -0.01, 0.03])
+    rs = np.random.RandomState(seed)
+    U = np.zeros((B, N, 3))
+    U[:, :, 2] = 0.9 * X0[:, 0:1] * Rocket6DoFConfig().g0
+    U[:, :, :2] = 0.05 * rs.randn(B, N, 2)
+    return X0, U
+
+
+def _staged_horizon_edge(p, X0, U, dt, atol_m):
+    """N = 257 (one step past the 256 whose controls a kernel stages in LDS: it reads them
+    from global memory) against N = 256 on the first 256 controls (staged): the arithmetic
+    is the same and only the source of u_k differs, so rows 0..256 are equal bit for bit.
+    Row 257 against the host loop at the file's tolerances for the model."""
+    assert U.shape[1] == 257
+    m257, c257 = p.propagate_batch(X0, U, None, dt)
+    m256, c256 = p.propagate_batch(X0, U[:, :256], None, dt)
+    np.testing.assert_array_equal(m257[:, :257], m256)
+    np.testing.assert_array_equal(c257[:, :257], c256)
+    p.use_device = False
+    mh, ch = p.propagate_batch(X0, U, None, dt)
+    print(f"row 257: means {np.abs(m257[:, 257] - mh[:, 257]).max():.3e}, covs rel "
+          f"{(np.abs(c257[:, 257] - ch[:, 257]) / np.maximum(np.abs(ch[:, 257]), 1e-300)).max():.3e}")
+    np.testing.assert_allclose(m257[:, 257], mh[:, 257], rtol=1e-10, atol=atol_m)
+    np.testing.assert_allclose(c257[:, 257], ch[:, 257], rtol=1e-7, atol=1e-15)
+
+
+def test_horizon_past_staged_controls_3dof(gpu_ctx):
+    """gpmpc_uprop3_linear, exact n = 300, B = 2, dt = 0.01."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    X0, U = _hover3(2, 257, 257)
+    p = UncertaintyPropagator(create_normalized_rocket(), _gp3_synthetic(300), ctx=gpu_ctx)
+    assert p._gate_3dof() is not None, "the device path would not be taken"
+    _staged_horizon_edge(p, X0, U, 0.01, 1e-10)
+
+
+def test_horizon_past_staged_controls_6dof(gpu_ctx):
+    """gpmpc_uprop6_linear, FITC M = 50, B = 2, dt = 0.01."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig, Rocket6DoFDynamics
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    from gp_mpc_rocket_landing_amd.rollouts6 import fit_structured_gp
+    X0, U = _hover6(2, 257, 257)
+    p = UncertaintyPropagator(Rocket6DoFDynamics(Rocket6DoFConfig()), fit_structured_gp(300, 50, seed=0, use_sparse=True),
+                              ctx=gpu_ctx)
+    assert p._gate_6dof() is not None, "the device path would not be taken"
+    _staged_horizon_edge(p, X0, U, 0.01, 1e-11)
+
+
+@pytest.mark.parametrize("n", [1024, 1025], ids=["n1024-last-count-in-registers", "n1025-first-count-read-per-step"])
+def test_row_count_boundary_3dof(gpu_ctx, n):
+    """The two sides of the 3-DoF register branch (4 rows a thread, 256 threads), vs the host loop."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    X0, U = _hover3(2, 3, n)
+    p = UncertaintyPropagator(create_normalized_rocket(), _gp3_synthetic(n), ctx=gpu_ctx)
+    assert p._gate_3dof() is not None, "the device path would not be taken"
+    md, cd = p.propagate_batch(X0, U, None, 0.1)
+    p.use_device = False
+    mh, ch = p.propagate_batch(X0, U, None, 0.1)
+    np.testing.assert_allclose(md, mh, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(cd, ch, rtol=1e-7, atol=1e-15)
+
+
+@pytest.mark.parametrize("M", [256, 257], ids=["fitc-M256-last-count-in-registers", "fitc-M257-first-count-read-per-step"])
+def test_row_count_boundary_6dof(gpu_ctx, M):
+    """The two sides of the 14-state register branch (one row a thread), vs the host loop."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import Rocket6DoFConfig, Rocket6DoFDynamics
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    from gp_mpc_rocket_landing_amd.rollouts6 import fit_structured_gp
+    X0, U = _hover6(2, 3, M)
+    p = UncertaintyPropagator(Rocket6DoFDynamics(Rocket6DoFConfig()), fit_structured_gp(600, M, seed=1, use_sparse=True),
+                              ctx=gpu_ctx)
+    assert p._gate_6dof() is not None, "the device path would not be taken"
+    md, cd = p.propagate_batch(X0, U, None, 0.1)
+    p.use_device = False
+    mh, ch = p.propagate_batch(X0, U, None, 0.1)
+    np.testing.assert_allclose(md, mh, rtol=1e-10, atol=1e-11)
+    np.testing.assert_allclose(cd, ch, rtol=1e-7, atol=1e-15)
+
+
+def test_one_row_gp_3dof(gpu_ctx):
+    """n = 1 through gpmpc_uprop3_linear (B = 1, N = 2): every thread but one has no row.  The
+    fit is well posed: K = sigma^2 + 1e-4 on one row, the target's std at its floor."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.mpc import UncertaintyPropagator
+    X0, U = _hover3(1, 2, 1)
+    p = UncertaintyPropagator(create_normalized_rocket(), _gp3_synthetic(1), ctx=gpu_ctx)
+    assert p._gate_3dof() is not None, "the device path would not be taken"
+    md, cd = p.propagate_batch(X0, U, None, 0.1)
+    p.use_device = False
+    mh, ch = p.propagate_batch(X0, U, None, 0.1)
+    assert np.all(np.isfinite(md)) and np.all(np.isfinite(cd))
+    np.testing.assert_allclose(md, mh, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(cd, ch, rtol=1e-7, atol=1e-15)

@@ -366,3 +366,34 @@ def test_propagate_dispatch(gpu_ctx, monkeypatch, gp3_exact, f1):
     for method in ("linear", "monte_carlo"):
         UncertaintyPropagator(dyn, gp3_exact, method=method, ctx=gpu_ctx).propagate(X0[0], U[0], None, 0.1)
     assert len(calls) == 1
+
+
+# ---- the horizon past the 256 steps whose controls the kernel stages in LDS ------------
+def test_horizon_past_staged_controls_3dof(gpu_ctx):
+    """gpmpc_uprop3_unscented, exact n = 300, B = 2, dt = 0.01, N = 257 (the controls read from
+    global memory) against N = 256 on the first 256 controls (staged in LDS): the same
+    arithmetic, so rows 0..256 are equal bit for bit and no factor fails in either run (the
+    numpy restatement over the same inputs finishes its 257 factors too).  Row 257 against
+    the host loop at the sharp tolerances."""
+    _ctx_default(gpu_ctx)
+    from gp_mpc_rocket_landing_amd.data import synthetic_training_data
+    from gp_mpc_rocket_landing_amd.dynamics import create_normalized_rocket
+    from gp_mpc_rocket_landing_amd.fleet import initial_conditions
+    from gp_mpc_rocket_landing_amd.gp import Simple3DoFGP
+    X, U, D = synthetic_training_data(300, seed=1)
+    gp = Simple3DoFGP(use_sparse=False)
+    gp.add_data(X, U, D); gp.fit()
+    B, N, dt = 2, 257, 0.01
+    X0 = initial_conditions(B)
+    rs = np.random.RandomState(257)
+    Uh = np.tile((-X0[:, 0:1] * np.array([-1.0, 0, 0]))[:, None, :], (1, N, 1)) * (1 + 0.1 * rs.randn(B, N, 1))
+    S0 = _spread(rs, B, 7, 1e-2)
+    p = _propagator(create_normalized_rocket(), gp, gpu_ctx, SHARP)
+    m257, c257, i257 = p._device_unscented(X0, Uh, S0, dt)
+    m256, c256, i256 = p._device_unscented(X0, Uh[:, :256], S0, dt)
+    assert not i257.any() and not i256.any()
+    np.testing.assert_array_equal(m257[:, :257], m256)
+    np.testing.assert_array_equal(c257[:, :257], c256)
+    p.use_device = False
+    mh, ch = p.propagate_unscented_batch(X0, Uh, S0, dt)
+    _assert_sharp((m257[:, 257], c257[:, 257]), (mh[:, 257], ch[:, 257]), "3-DoF N=257, row 257")
