@@ -5,6 +5,7 @@ closed-loop path are computed on the device inside the fleet step).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -24,14 +25,40 @@ class AtmosphereModel:
         return self.rho_0 * np.exp(-np.asarray(altitude) / self.scale_height)
 
 
+# The 6-DoF extractors round as the reference's per-row code does, so that a fit on the same
+# rows under the same seed draws the same k-means inducing points bit for bit (F9b,
+# tests/test_gpu_uprop6_reference.py): the reference squares numpy scalars with ``** 2``, which
+# is libm's pow (not always the correctly rounded product), takes norms with np.linalg.norm
+# (BLAS dot) and rotates with ``C @ v`` (BLAS gemv).  The three helpers below are those
+# operations over P rows.
+_libm_pow = np.frompyfunc(math.pow, 2, 1)
+
+
+def _sq(a):
+    """a ** 2 as on a numpy float64 scalar: libm pow(a, 2)."""
+    return _libm_pow(np.asarray(a, float), 2.0).astype(float)
+
+
+def _norm3(a):
+    """np.linalg.norm of every row of a (P, 3): sqrt of the BLAS dot product."""
+    a = np.ascontiguousarray(a, dtype=float)
+    return np.sqrt(np.matmul(a[:, None, :], a[:, :, None])[:, 0, 0])
+
+
 def _dcm(q):
     """Body-from-inertial DCM of quaternions [w, x, y, z] (features.py:265-270), (P,3,3)."""
     w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    xx, yy, zz = _sq(x), _sq(y), _sq(z)
     return np.stack([
-        np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + w * z), 2 * (x * z - w * y)], -1),
-        np.stack([2 * (x * y - w * z), 1 - 2 * (x * x + z * z), 2 * (y * z + w * x)], -1),
-        np.stack([2 * (x * z + w * y), 2 * (y * z - w * x), 1 - 2 * (x * x + y * y)], -1),
+        np.stack([1 - 2 * (yy + zz), 2 * (x * y + w * z), 2 * (x * z - w * y)], -1),
+        np.stack([2 * (x * y - w * z), 1 - 2 * (xx + zz), 2 * (y * z + w * x)], -1),
+        np.stack([2 * (x * z + w * y), 2 * (y * z - w * x), 1 - 2 * (xx + yy)], -1),
     ], axis=1)
+
+
+def _body_velocity(q, v):
+    """C_BI @ v_I per row (BLAS gemv, as the reference's ``@``)."""
+    return np.matmul(np.ascontiguousarray(_dcm(q)), np.ascontiguousarray(v, dtype=float)[:, :, None])[:, :, 0]
 
 
 class RocketFeatureExtractor:
@@ -62,6 +89,14 @@ class RocketFeatureExtractor:
         speed = np.sqrt(np.sum(v * v, axis=1))
         rho = self.atmosphere.density_array(alt)
         qn = (0.5 * rho * speed ** 2) / (0.5 * self.atmosphere.rho_0 * self.v_ref ** 2)
+        return alt, v, speed, rho, qn
+
+    def _common6(self, X):
+        """_common with the reference's rounding of |v| and |v|^2 (the 6-DoF extractors)."""
+        alt, v = X[:, 1], X[:, 4:7]
+        speed = _norm3(v)
+        rho = self.atmosphere.density_array(alt)
+        qn = (0.5 * rho * _sq(speed)) / (0.5 * self.atmosphere.rho_0 * self.v_ref ** 2)
         return alt, v, speed, rho, qn
 
 
@@ -103,12 +138,12 @@ class TranslationalFeatureExtractor(RocketFeatureExtractor):
 
     def extract_batch(self, X, U):
         X = np.atleast_2d(np.asarray(X, float)); U = np.atleast_2d(np.asarray(U, float))
-        alt, v, speed, rho, qn = self._common(X)
-        vB = np.einsum("pij,pj->pi", _dcm(X[:, 7:11]), v)
+        alt, v, speed, rho, qn = self._common6(X)
+        vB = _body_velocity(X[:, 7:11], v)
         moving = speed > 1e-3
         aoa = np.where(moving, np.arctan2(-vB[:, 2], vB[:, 0]), 0.0)
         beta = np.where(moving, np.arcsin(np.clip(vB[:, 1] / np.where(moving, speed, 1.0), -1, 1)), 0.0)
-        tm = np.sqrt(np.sum(U * U, axis=1))
+        tm = _norm3(U)
         cols = [v[:, 0] / self.v_ref, v[:, 1] / self.v_ref, v[:, 2] / self.v_ref,
                 speed / self.v_ref, qn, aoa, beta, U[:, 0] / 10.0, U[:, 1] / 10.0,
                 U[:, 2] / 10.0, tm / 10.0]
@@ -129,10 +164,10 @@ class RotationalFeatureExtractor(RocketFeatureExtractor):
 
     def extract_batch(self, X, U):
         X = np.atleast_2d(np.asarray(X, float)); U = np.atleast_2d(np.asarray(U, float))
-        alt, v, speed, rho, qn = self._common(X)
+        alt, v, speed, rho, qn = self._common6(X)
         w = X[:, 11:14]
-        wm = np.sqrt(np.sum(w * w, axis=1))
-        vB = np.einsum("pij,pj->pi", _dcm(X[:, 7:11]), v)
+        wm = _norm3(w)
+        vB = _body_velocity(X[:, 7:11], v)
         cols = [w[:, 0], w[:, 1], w[:, 2], wm, U[:, 0] / 10.0, U[:, 1] / 10.0, U[:, 2] / 10.0,
                 vB[:, 0] / self.v_ref, vB[:, 1] / self.v_ref, vB[:, 2] / self.v_ref,
                 speed / self.v_ref, qn]

@@ -8,7 +8,8 @@ UncertaintyPropagator._propagate_linear, uncertainty_prop.py:117-177:
 
 with the residual rows 4:7 (v-dot) and, for the 14-state model, 11:14
 (omega-dot).  Pinned to the reference's own output in
-tests/golden/f9_uncertainty_prop.npz.
+tests/golden/f9_uncertainty_prop.npz, and on the 14-state rocket (SixDofPlant over the
+structured predictors) in tests/golden/f9b_uprop6.npz.
 """
 from __future__ import annotations
 
@@ -53,7 +54,42 @@ def structured_exact_predictor(X, U, Dv, Dw, noise=1e-4):
         mv, vv = gp_oracle.exact_predict(sv, gp_oracle.features_translational(x, u))
         mw, vw = gp_oracle.exact_predict(sw, gp_oracle.features_rotational(x, u))
         return mv[0], mw[0], vv[0], vw[0]
+    predict.states = (sv, sw)
     return predict
+
+
+def structured_fitc_predictor(Zi_v, Zi_w, X, U, Dv, Dw, noise=1e-4):
+    """StructuredRocketGP(use_sparse=True) fit on (X, U, Dv, Dw) over the inducing points
+    Zi_v (M, 13) / Zi_w (M, 12) as a gp_predict callable (structured_gp.py:206-268 over
+    sparse_gp.py:150-305).  The mean is the one the surface returns: K*u alpha as written."""
+    sv = gp_oracle.fitc_fit(np.asarray(Zi_v, float), gp_oracle.features_translational(X, U), Dv, noise=noise)
+    sw = gp_oracle.fitc_fit(np.asarray(Zi_w, float), gp_oracle.features_rotational(X, U), Dw, noise=noise)
+
+    def predict(x, u):
+        x = np.atleast_2d(x); u = np.atleast_2d(u)
+        mv, vv = gp_oracle.fitc_predict(sv, gp_oracle.features_translational(x, u))
+        mw, vw = gp_oracle.fitc_predict(sw, gp_oracle.features_rotational(x, u))
+        return mv[0], mw[0], vv[0], vw[0]
+    predict.states = (sv, sw)
+    return predict
+
+
+class SixDofPlant:
+    """step / linearize of the 14-state rocket over sixdof_oracle alone: a plant for the
+    restatements that shares no code with gp_mpc_rocket_landing_amd.dynamics.  rk: a
+    sixdof_oracle.rocket_params set (None: the default rocket)."""
+    n_state = 14
+
+    def __init__(self, rk=None):
+        self.rk = rk
+
+    def step(self, x, u, dt):
+        from . import sixdof_oracle
+        return sixdof_oracle.step(np.asarray(x, float), np.asarray(u, float), dt, self.rk)
+
+    def linearize(self, x, u, dt=0.1):
+        from . import sixdof_oracle
+        return sixdof_oracle.linearize(np.asarray(x, float), np.asarray(u, float), dt, self.rk)
 
 
 def simple3dof_exact_predictor(X, U, D, noise=1e-4):

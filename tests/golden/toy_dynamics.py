@@ -4,7 +4,10 @@ The reference's 6-DoF plant lives in the absent ``simdyn`` package, so the F9
 fixture drives the reference UncertaintyPropagator with this 14-state model
 (mass, position, velocity, attitude quaternion, body rates; explicit Euler,
 central-difference Jacobians) and the tests drive the mirror with the same
-one.  Test infrastructure only.
+one.  The device recursions take Rocket6DoFDynamics only, so F9 reaches the
+per-step host loop; the 14-state device path is pinned to the reference by F9b
+(f9b_uprop6.npz, gen_uprop6_golden.py: the reference propagator over this
+package's Rocket6DoFDynamics).  Test infrastructure only.
 """
 from __future__ import annotations
 

@@ -43,19 +43,21 @@ def ut_weights(n, ut=REFERENCE_UT):
     return lam, w_m, w_c
 
 
-def propagate_unscented(dynamics, gp_predict, x0, U, Sigma_0=None, dt=0.1, ut=REFERENCE_UT, reverse_sum=False):
+def propagate_unscented(dynamics, gp_predict, x0, U, Sigma_0=None, dt=0.1, ut=REFERENCE_UT, reverse_sum=False,
+                        factor=np.linalg.cholesky, weights=ut_weights):
     """uncertainty_prop.py:179-264 -> means (N+1, n), covariances (N+1, n, n).  Raises
-    np.linalg.LinAlgError where the reference's np.linalg.cholesky does."""
+    np.linalg.LinAlgError where the reference's np.linalg.cholesky does.  factor / weights:
+    the two places a mutant of the transform replaces (tests/uprop6_check.py)."""
     x0 = np.asarray(x0, float); U = np.asarray(U, float).reshape(-1, 3)
     n, N = x0.size, len(U)
     S = np.eye(n) * 1e-6 if Sigma_0 is None else np.array(Sigma_0, float)
-    lam, w_m, w_c = ut_weights(n, ut)
+    lam, w_m, w_c = weights(n, ut)
     means = np.zeros((N + 1, n)); covs = np.zeros((N + 1, n, n))
     means[0] = x0; covs[0] = S
     x = x0.copy()
     for k in range(N):
         u = U[k]
-        L = np.linalg.cholesky((n + lam) * S + 1e-10 * np.eye(n))
+        L = factor((n + lam) * S + 1e-10 * np.eye(n))
         sp = np.zeros((2 * n + 1, n))
         sp[0] = x
         for i in range(n):
