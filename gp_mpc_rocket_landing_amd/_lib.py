@@ -106,6 +106,20 @@ class SafetyConfig(ctypes.Structure):
                 ("n_iters", ctypes.c_int), ("lr", ctypes.c_double), ("fd_eps", ctypes.c_double)]
 
 
+class BaselineConfig(ctypes.Structure):
+    """gpmpc_baseline_config: controller kind, batch, the plant's scalars, clips, PID gains and
+    the dispersed plant's switches."""
+    _fields_ = [("kind", ctypes.c_int), ("batch", ctypes.c_int), ("max_steps", ctypes.c_int), ("dt", ctypes.c_double),
+                ("alpha", ctypes.c_double), ("g", ctypes.c_double * 3), ("T_lo", ctypes.c_double),
+                ("T_hi", ctypes.c_double), ("gimbal_max", ctypes.c_double), ("Kp_z", ctypes.c_double),
+                ("Ki_z", ctypes.c_double), ("Kd_z", ctypes.c_double), ("Kp_xy", ctypes.c_double),
+                ("Ki_xy", ctypes.c_double), ("Kd_xy", ctypes.c_double), ("max_integral", ctypes.c_double),
+                ("thrust_min", ctypes.c_double), ("thrust_max", ctypes.c_double), ("pid_dt", ctypes.c_double),
+                ("pid_g", ctypes.c_double), ("n_ref", ctypes.c_int), ("thrust_rows", ctypes.c_int),
+                ("wind_kind", ctypes.c_int), ("wind_rows", ctypes.c_int), ("drag", ctypes.c_int),
+                ("sim_thrust", ctypes.c_double), ("sim_aero", ctypes.c_double), ("log", ctypes.c_int)]
+
+
 def _sig(name, res, *args):
     f = getattr(_L, name)
     f.restype = res
@@ -218,6 +232,9 @@ _sig("gpmpc_tube_linear", _c, _vp, _dp, _c, _c, ctypes.c_double, ctypes.c_double
      _dp, _dp, _dp)
 _sig("gpmpc_tube_mc", _c, _vp, _dp, _c, _c, _c, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _dp)
 _sig("gpmpc_tube_plan", _c, _c, _c, _ip, _ip)
+_sig("gpmpc_baseline_default_config", None, ctypes.POINTER(BaselineConfig))
+_sig("gpmpc_baseline_fly", _c, _vp, ctypes.POINTER(BaselineConfig), _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip,
+     _dp, _dp)
 _sig("gpmpc_rollout6_default_config", None, ctypes.POINTER(Rollout6Config))
 _sig("gpmpc_rollout6_create", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
 _sig("gpmpc_rollout6_create_exact", _c, _vp, _vp, _vp, ctypes.POINTER(Rollout6Config), _c, ctypes.POINTER(_vp))
@@ -264,7 +281,8 @@ EXPORTED = ["gpmpc_abi_version", "gpmpc_last_error", "gpmpc_ctx_create", "gpmpc_
             "gpmpc_knn_destroy", "gpmpc_knn_query", "gpmpc_knn_interp", "gpmpc_knn_plan",
             "gpmpc_hull_project", "gpmpc_knn_set_points", "gpmpc_knn_hull", "gpmpc_hull_plan",
             "gpmpc_safety_default_config", "gpmpc_safety_filter", "gpmpc_safety_simulate",
-            "gpmpc_tube_linear", "gpmpc_tube_mc", "gpmpc_tube_plan"]
+            "gpmpc_tube_linear", "gpmpc_tube_mc", "gpmpc_tube_plan",
+            "gpmpc_baseline_default_config", "gpmpc_baseline_fly"]
 
 
 class HIPError(RuntimeError):
@@ -1469,3 +1487,65 @@ def tube_mc(ctx, rocket, X_nom, U_nom, noise, dt, quantile=0.95):
     _chk(_L.gpmpc_tube_mc(ctx.h, _d(rk), B, N, noise.shape[2], float(dt), float(quantile), _d(X_nom), _d(U_nom),
                           _d(noise), _d(tubes)), "tube_mc")
     return tubes
+
+
+# ---- baseline controllers and dispersed plants (csrc/baseline.hip) ------------------------------
+def baseline_default_config(**kw):
+    """gpmpc_baseline_config at the library defaults with the keyword fields replaced."""
+    c = BaselineConfig()
+    _L.gpmpc_baseline_default_config(ctypes.byref(c))
+    return set_fields(c, kw)
+
+
+def baseline_fly(ctx, x0, kind, max_steps, dt, alpha=1.0 / 30.0, g=(-1.0, 0.0, 0.0), K=None, u_hover=None,
+                 T_lo=0.0, T_hi=6.5, gimbal_max=0.5, pid=None, U_ref=None, thrust_table=None, wind_table=None,
+                 wind_rows=None, wind_altitude_factor=False, drag_cda=None, sim_thrust=0.0, sim_aero=0.0, noise=None,
+                 log=True, timing=None):
+    """gpmpc_baseline_fly: B landings from x0 (B, 7) under one baseline controller in one device
+    call.  kind 0 LQR (K (B, 3, 7), u_hover (B, 3), the clips), 1 PID (pid: the
+    gpmpc_baseline_config gain fields by name), 2 open loop (U_ref (n, 3)).  The dispersed plant:
+    thrust_table (>= B + max_steps, 4), wind_table (rows, 3) with wind_rows (max_steps,) and
+    wind_altitude_factor, drag_cda (B,); the simulator's own dispersions: sim_thrust, sim_aero
+    over noise (B, max_steps, 4).  -> records (B, 16), nsteps (B,), log (max_steps, B, 10) or
+    None (rows past nsteps.max() are not written).  timing: a dict that receives "kernel_ms"."""
+    x0 = f64(np.atleast_2d(x0))
+    B, T = x0.shape[0], int(max_steps)
+    if x0.shape != (B, 7):
+        raise ValueError(f"baseline_fly: x0 shape {x0.shape}, expected (B, 7)")
+    cfg = baseline_default_config(kind=int(kind), batch=B, max_steps=T, dt=float(dt), alpha=float(alpha), g=g,
+                                  T_lo=float(T_lo), T_hi=float(T_hi), gimbal_max=float(gimbal_max),
+                                  sim_thrust=float(sim_thrust), sim_aero=float(sim_aero), log=int(bool(log)))
+    if pid:
+        set_fields(cfg, {k: float(v) for k, v in pid.items()})
+
+    def arr(a, shape, what, dtype=np.float64):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if any(s is not None and s != t for s, t in zip(shape, a.shape)) or a.ndim != len(shape):
+            raise ValueError(f"baseline_fly: {what} shape {a.shape}, expected {shape}")
+        return a
+
+    K = arr(K, (B, 3, 7), "K")
+    u_hover = arr(u_hover, (B, 3), "u_hover")
+    U_ref = arr(U_ref, (None, 3), "U_ref")
+    thrust_table = arr(thrust_table, (None, 4), "thrust_table")
+    wind_table = arr(wind_table, (None, 3), "wind_table")
+    wind_rows = arr(wind_rows, (T,), "wind_rows", np.int32)
+    drag_cda = arr(drag_cda, (B,), "drag_cda")
+    noise = arr(noise, (B, T, 4), "noise")
+    cfg.n_ref = 0 if U_ref is None else len(U_ref)
+    cfg.thrust_rows = 0 if thrust_table is None else len(thrust_table)
+    if wind_table is not None:
+        cfg.wind_kind, cfg.wind_rows = (2 if wind_altitude_factor else 1), len(wind_table)
+    cfg.drag = int(drag_cda is not None)
+    rec = np.zeros((B, 16)); ns = np.zeros(B, np.int32)
+    logbuf = np.empty((T, B, 10)) if log and B * T > 0 else None
+    ms = np.zeros(1)
+    p = lambda a, f=_d: None if a is None else f(a)   # noqa: E731
+    _chk(_L.gpmpc_baseline_fly(ctx.h, ctypes.byref(cfg), _d(x0), p(K), p(u_hover), p(U_ref), p(thrust_table),
+                               p(wind_table), p(wind_rows, _i), p(drag_cda), p(noise), _d(rec), _i(ns), p(logbuf),
+                               _d(ms) if timing is not None else None), "baseline_fly")
+    if timing is not None:
+        timing["kernel_ms"] = float(ms[0])
+    return rec, ns, logbuf

@@ -562,15 +562,100 @@ class MonteCarloSimulator:
                                          wall_ms / n, None if per_step is None else per_step[i])
                 for i in range(n)]
 
+    # ---- the baseline controllers' batch (csrc/baseline.hip) ----------
+    def _baseline_plan(self, n_workers: int = 1):
+        """(controller kind, "") when the landings can fly in one ``baseline_fly`` call, else
+        (None, reason).  Host logic only: no device call."""
+        from ..dynamics.rocket_3dof import Rocket3DoFDynamics
+        from .baselines import device_gate
+        from .dispersion import DispersedDynamics
+        cfg = self.config
+        kind, why = device_gate(self.controller)
+        if kind is None:
+            return None, why
+        if type(self.dynamics) is DispersedDynamics:
+            return None, ("a DispersedDynamics instance's step_count runs on across landings: serial "
+                          "(DispersionAnalysis.run_single batches one instance per landing)")
+        if type(self.dynamics) is not Rocket3DoFDynamics:
+            return None, "the plant is not Rocket3DoFDynamics"
+        if self.safety_filter is not None:
+            return None, "a safety filter is set"
+        if n_workers != 1 and (cfg.thrust_dispersion > 0 or cfg.aero_dispersion > 0):
+            return None, "n_workers > 1 with dispersions: one serial noise stream"
+        if int(cfg.max_time / cfg.dt) < 1:
+            return None, "no control step fits in max_time"
+        return kind, ""
+
+    def _run_baselines(self, kind, x0s, plant=None, noise=None, timing=None):
+        """The landings from ``x0s`` in one device call -> [SimulationResult].  ``plant``: the
+        ``DispersedDynamics`` batch (``dispersion.plant_batch``) or None for the bare plant
+        with the config's own dispersions over ``noise``.  The controller is initialised per
+        landing on the host, as ``run_single`` does.  ``timing``: a dict that receives the
+        host preparation, kernel and total milliseconds."""
+        from .. import _lib
+        from .baselines import controller_batch
+        cfg = self.config
+        n = len(x0s)
+        t0 = time.perf_counter()
+        x0s = np.asarray(x0s, float).reshape(n, 7)
+        p = self.dynamics.params
+        kw = controller_batch(self.controller, kind, x0s)
+        kw.update(plant or {})
+        if plant is None and (cfg.thrust_dispersion > 0 or cfg.aero_dispersion > 0):
+            kw.update(sim_thrust=cfg.thrust_dispersion, sim_aero=cfg.aero_dispersion, noise=noise)
+        max_steps = int(cfg.max_time / cfg.dt)
+        t1 = time.perf_counter()
+        tm = {} if timing is not None else None
+        rec, ns, log = _lib.baseline_fly(_lib.default_context(), x0s, max_steps=max_steps, dt=float(cfg.dt),
+                                         alpha=float(p.alpha), g=np.asarray(p.g_vec, float), timing=tm, **kw)
+        wall_ms = (time.perf_counter() - t0) * 1000
+        if timing is not None:
+            timing.update(prepare_ms=(t1 - t0) * 1000, kernel_ms=tm["kernel_ms"], call_ms=wall_ms - (t1 - t0) * 1000)
+        if self.keep_raw_log:
+            self.last_raw_log = dict(records=rec, log=log, nsteps=ns)
+        out = []
+        for i in range(n):
+            T = int(ns[i])
+            states = np.concatenate([x0s[i:i + 1], log[:T, i, :7]], axis=0)
+            out.append(self._result_from_record(i, rec[i], states, log[:T, i, 7:].copy(), wall_ms / n))
+            out[-1].metadata = {}
+        return out
+
     def run(self, n_runs: int = 1000, n_workers: int = 1, seed: int = 42,
             progress_callback: Optional[Callable[[int, int], None]] = None,
             use_fleet: bool = True) -> MonteCarloResults:
         """monte_carlo.py:585-636.  ``use_fleet=False`` forces the reference's loop.  On
         the batched path ``progress_callback(terminated, n_runs)`` is called once per
-        chunk of control steps and ``compute_time_ms`` is the run's wall time / n_runs."""
+        chunk of control steps and ``compute_time_ms`` is the run's wall time / n_runs.
+        A baseline controller (``_baseline_plan``) flies its landings in one device call:
+        ``last_path`` "baselines", one ``progress_callback(n_runs, n_runs)``."""
         from .. import _lib
         plan, second = self._fleet_plan(n_workers) if use_fleet else (None, "use_fleet=False")
         why = second if plan is None else ""
+        kind, bwhy = self._baseline_plan(n_workers) if use_fleet and plan is None else (None, "")
+        if kind is not None:
+            cfg = self.config
+            if n_workers == 1:
+                x0s = [sample_initial_condition(seed + i, cfg) for i in range(n_runs)]
+                disp = cfg.thrust_dispersion > 0 or cfg.aero_dispersion > 0
+                noise = mc_noise_table(seed, n_runs, cfg) if disp else None
+            else:   # the reference draws every initial condition from one stream seeded `seed`
+                print(f"Running {n_runs} simulations with {n_workers} workers...")
+                np.random.seed(seed)
+                x0s = [self.sample_initial_condition() for _ in range(n_runs)]
+                noise = None
+            try:
+                results = self._run_baselines(kind, x0s, noise=noise) if n_runs > 0 else []
+                self.last_path, self.last_path_reason = "baselines", ""
+                if progress_callback is not None:
+                    progress_callback(n_runs, n_runs)
+                return MonteCarloResults(config=self.config, results=results)
+            except _lib.HIPError as e:
+                if e.rc != -2:   # only "the library refuses these arguments" falls back
+                    raise
+                why = f"the device refused the configuration: {e}"
+        elif use_fleet and plan is None and type(self.controller).__module__.endswith("experiments.baselines"):
+            why = bwhy   # a baseline controller the batch does not admit: its own reason
         if plan is not None:
             cfg = self.config
             if n_workers == 1:
@@ -634,22 +719,43 @@ class MonteCarloSimulator:
 
 
 def compare_controllers(dynamics, controllers: Dict[str, Any], n_runs: int = 100,
-                        config: Optional[SimulationConfig] = None, seed: int = 42) -> Dict[str, MonteCarloResults]:
+                        config: Optional[SimulationConfig] = None, seed: int = 42,
+                        use_fleet: bool = True) -> Dict[str, MonteCarloResults]:
     """monte_carlo.py:679-732: every controller flies the same initial conditions (one
-    stream seeded ``seed``), one ``run_single`` per landing."""
+    stream seeded ``seed``), one ``run_single`` per landing.  With ``use_fleet`` a baseline
+    controller that ``_baseline_plan`` admits (and a config without dispersions: those draw
+    from one stream across landings) flies them in one device call; every other controller,
+    the GP-MPC included, takes ``run_single`` as before.  ``compare_controllers.last_paths``
+    holds the path of each controller of the last call."""
+    from .. import _lib
     config = config or SimulationConfig()
     np.random.seed(seed)
     sampler = MonteCarloSimulator(dynamics, None, config)
     initial_states = [sampler.sample_initial_condition() for _ in range(n_runs)]
     out = {}
+    paths = compare_controllers.last_paths = {}
     for name, controller in controllers.items():
         print(f"\nEvaluating controller: {name}")
         sim = MonteCarloSimulator(dynamics, controller, config)
-        runs = []
-        for i, x0 in enumerate(initial_states):
-            runs.append(sim.run_single(i, x0=x0.copy()))
-            if (i + 1) % 50 == 0:
-                print(f"  Completed {i + 1}/{n_runs}...")
+        runs = None
+        kind, why = sim._baseline_plan(1) if use_fleet else (None, "use_fleet=False")
+        if kind is not None and (config.thrust_dispersion > 0 or config.aero_dispersion > 0):
+            kind, why = None, "the config's dispersions draw from one stream across landings"
+        if kind is not None and n_runs > 0:
+            try:
+                runs = sim._run_baselines(kind, [x0.copy() for x0 in initial_states])
+                paths[name] = ("baselines", "")
+            except _lib.HIPError as e:
+                if e.rc != -2:
+                    raise
+                why = f"the device refused the configuration: {e}"
+        if runs is None:
+            paths[name] = ("loop", why)
+            runs = []
+            for i, x0 in enumerate(initial_states):
+                runs.append(sim.run_single(i, x0=x0.copy()))
+                if (i + 1) % 50 == 0:
+                    print(f"  Completed {i + 1}/{n_runs}...")
         out[name] = MonteCarloResults(config=config, results=runs)
         print(f"  Success rate: {out[name].success_rate * 100:.1f}%")
     return out

@@ -942,6 +942,67 @@ int gpmpc_tube_mc(gpmpc_ctx *ctx, const double *rocket, int batch, int N, int n_
                   const double *X_nom, const double *U_nom, const double *noise, double *tubes);
 int gpmpc_tube_plan(int N, int n_samples, int *k_tile, int *mc_cap);
 
+/* ---- baseline controllers and dispersed plants --------------------
+ * The landings of MonteCarloSimulator.run_single (reference src/experiments/monte_carlo.py)
+ * for a controller with `solve` and no `step`, under the reference's baseline controllers
+ * (src/experiments/baselines.py) and, optionally, its DispersedDynamics (src/experiments/
+ * dispersion.py) around the 3-DoF Euler plant m+ = m - dt alpha |u|, r+ = r + dt v,
+ * v+ = v + dt (u / m + g).  One call flies batch landings from x0 (batch x 7) to termination
+ * in one launch: host buffers, one upload, one read-back of the records and step counts and
+ * one of the log's used rows.
+ *
+ * Per control step and landing: the termination tests of the fleet (records' outcomes 1..6:
+ * step == max_steps, altitude < 0, m <= 1.01, |x| > 1e6 or NaN, the landing window), the
+ * target x with zero velocity and altitude max(0.5, altitude - 2), the control law, the plant
+ * step, the append of (x_next, commanded u).
+ *   kind LQR: u = u_hover - K (x - target), u[0] clipped to [T_lo, T_hi], u[1:] to
+ *     +-gimbal_max; K (batch x 3 x 7) and u_hover (batch x 3) per landing.
+ *   kind PID: integral += position error x pid_dt, clipped to +-max_integral; vertical
+ *     m (pid_g + Kp_z e + Ki_z I + Kd_z de) clipped to [thrust_min, thrust_max], lateral
+ *     (Kp_xy e + Ki_xy I + Kd_xy de) m clipped to +-0.3 thrust_max; de = the velocity error.
+ *   kind OPEN_LOOP: row min(step, n_ref - 1) of U_ref (n_ref x 3).
+ * Plant: with thrust_rows != 0 the control becomes u[0] *= t[0], u[1] += t[1], u[2] += t[2],
+ * u[0] *= t[3] with t = thrust_table[i + s] (landing i, plant step s = 1..max_steps;
+ * thrust_rows >= batch + max_steps rows of 4); the Euler step; wind_kind 1: v += w dt with
+ * w = wind_table[i + wind_step_rows[s - 1]] (wind_rows x 3), wind_kind 2: the same with w
+ * times min(1, max(x[3], 10) / 100); drag != 0: when |v| > 1 on the pre-step state,
+ * v -= (drag_cda[i] |v|^2 / m) (v / |v|) dt.  sim_thrust / sim_aero > 0: the fleet's
+ * Monte-Carlo draws from noise (batch x max_steps x 4, gpmpc_fleet_mc_attach).
+ *
+ * records (batch x GPMPC_REC_LEN, the fleet layout; the solver slots 11, 12, 14, 15 are 0),
+ * nsteps (batch), log (max_steps x batch x 10, step-major: x_next (7), u (3); rows past the
+ * longest landing are not written; may be NULL with log = 0), kernel_ms (the launch between
+ * two events, or NULL).
+ * -2 with gpmpc_last_error set, before any launch, for a null pointer, batch < 1,
+ * max_steps < 1, dt <= 0, an unknown kind, an empty open-loop table, a non-finite K, u_hover
+ * or x0, a table shorter than its indices reach. */
+#define GPMPC_BASELINE_LQR 0
+#define GPMPC_BASELINE_PID 1
+#define GPMPC_BASELINE_OPEN_LOOP 2
+typedef struct {
+  int kind;               /* GPMPC_BASELINE_* */
+  int batch;
+  int max_steps;          /* 300 */
+  double dt;              /* 0.1 */
+  double alpha;           /* 1/30 */
+  double g[3];            /* -1, 0, 0 */
+  double T_lo, T_hi, gimbal_max;                          /* LQR clips: 0, 6.5, 0.5 */
+  double Kp_z, Ki_z, Kd_z, Kp_xy, Ki_xy, Kd_xy;           /* PIDConfig defaults */
+  double max_integral, thrust_min, thrust_max, pid_dt, pid_g;
+  int n_ref;              /* rows of U_ref */
+  int thrust_rows;        /* 0: no thrust dispersion */
+  int wind_kind;          /* 0 none, 1 table, 2 table x altitude factor */
+  int wind_rows;
+  int drag;               /* 0 */
+  double sim_thrust, sim_aero;                            /* SimulationConfig's dispersions, 0 */
+  int log;                /* 1 */
+} gpmpc_baseline_config;
+void gpmpc_baseline_default_config(gpmpc_baseline_config *cfg);
+int gpmpc_baseline_fly(gpmpc_ctx *ctx, const gpmpc_baseline_config *cfg, const double *x0, const double *K,
+                       const double *u_hover, const double *U_ref, const double *thrust_table,
+                       const double *wind_table, const int *wind_step_rows, const double *drag_cda,
+                       const double *noise, double *records, int *nsteps, double *log, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
