@@ -335,6 +335,18 @@ def new_rollout(x0, N=30):
                 rho=admm_ref.default_settings().rho, rec=rec, X=None)
 
 
+def pre_step_outcome(x, m0):
+    """The checks at the top of a step on the 14-state rocket: monte_carlo.py:458-488 on
+    [m, r, v] (mc_oracle.pre_step_outcome), then DIVERGENCE for any of the 14 states
+    above 1e6 or NaN -- after the landing check, so near the ground a landing verdict
+    wins over a diverged attitude.  Returns 0 (the step runs) or an outcome code."""
+    from . import mc_oracle
+    o = mc_oracle.pre_step_outcome(x[:7], m0)
+    if o == 0 and (np.any(np.abs(x) > 1e6) or np.any(np.isnan(x))):
+        o = mc_oracle.DIVERGENCE
+    return o
+
+
 def rollout_step(gpv, gpw, S, dt=0.1, max_steps=300, qp_settings=None, corrected=True, upright=False, rk=None):
     """One control step of the 6-DoF rollout (monte_carlo.py:455-537 termination
     rules on the first seven states; one GPMPC.solve pass as the module header)."""
@@ -345,9 +357,7 @@ def rollout_step(gpv, gpw, S, dt=0.1, max_steps=300, qp_settings=None, corrected
     if rec[0] != 0:
         return out, None
     m0 = rec[13]
-    o = mc_oracle.TIMEOUT if rec[1] >= max_steps else mc_oracle.pre_step_outcome(x[:7], m0)
-    if o == 0 and (np.any(np.abs(x) > 1e6) or np.any(np.isnan(x))):
-        o = mc_oracle.DIVERGENCE
+    o = mc_oracle.TIMEOUT if rec[1] >= max_steps else pre_step_outcome(x, m0)
     if o:
         rec[0] = o; rec[2] = m0 - x[0]; rec[4:11] = x[:7]
         return out, None

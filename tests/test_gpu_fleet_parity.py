@@ -250,6 +250,81 @@ def test_fleet_steps_match_oracle_to_termination(gpu_ctx):
         fl.close()
 
 
+@pytest.mark.parametrize("solver", ["0", "1"])
+def test_fleet_termination_ladder_at_step0(gpu_ctx, solver):
+    """The termination table (termination_cases.py, its seven-state rows) in one fleet,
+    one step, under both copies of the ladder: GPMPC_FLEET_SOLVER=0 (k_fleet_control,
+    fleet.hip) and 1 (k_fleet_control2, fleet_control.h).  Every row's outcome is the
+    table's literal.  A terminated row's record holds its state bit for bit and
+    m0 - m, with no step, time or iteration counted, and its state, plan, duals and rho
+    are untouched; a row that continues matches the oracle's step
+    (mc_oracle.landing_step) as in test_fleet_steps_match_oracle_to_termination, and where
+    its QP has no solution (alt 1e6, vx -1e6: status -3) the record holds the state and
+    the status while state, plan, duals and rho stay bit for bit as they were."""
+    import os
+    import termination_cases as tc
+    from gp_mpc_rocket_landing_amd.data import synthetic_training_data
+    from gp_mpc_rocket_landing_amd.fleet import Fleet, fit_gp
+    from oracle import gp_oracle, mc_oracle
+
+    def bits(a):
+        return np.ascontiguousarray(np.asarray(a, float)).view(np.uint64)
+
+    cases = tc.SEVEN_STATE
+    x0 = tc.states7(cases)
+    X, U, D = synthetic_training_data(1000, seed=0)
+    st = gp_oracle.exact_fit(gp_oracle.features_3dof(X, U), D)
+    gp = fit_gp(gpu_ctx, n_train=1000)
+    os.environ["GPMPC_FLEET_SOLVER"] = solver
+    try:
+        fl = Fleet(gpu_ctx, gp, len(cases), max_steps=300)
+    finally:
+        os.environ.pop("GPMPC_FLEET_SOLVER", None)
+    try:
+        fl.reset(x0)
+        S = fl.state()
+        fl.step(1)
+        T = fl.state()
+    finally:
+        fl.close()
+    np.testing.assert_array_equal(bits(S["x"]), bits(x0))
+    seen, live, failed = set(), 0, 0
+    for b, c in enumerate(cases):
+        with np.errstate(invalid="ignore", over="ignore"):
+            want, info = mc_oracle.landing_step(st, _landing(S, b))
+        got = _landing(T, b)
+        np.testing.assert_array_equal(got["rec"][[0, 1, 11, 12, 13, 14]], want["rec"][[0, 1, 11, 12, 13, 14]],
+                                      err_msg=c.name)
+        seen.add(int(got["rec"][0]))
+        if c.code:
+            assert got["rec"][0] == c.code and info is None, (c.name, got["rec"][0])
+            np.testing.assert_array_equal(bits(got["rec"][4:11]), bits(x0[b]), err_msg=c.name)
+            with np.errstate(invalid="ignore"):
+                np.testing.assert_array_equal(got["rec"][2], x0[b, 0] - x0[b, 0], err_msg=c.name)
+            assert np.all(got["rec"][[1, 3, 11, 12, 14, 15]] == 0), (c.name, got["rec"])
+            for key in ("x", "Xw", "Uw", "y", "rho"):
+                np.testing.assert_array_equal(bits(got[key]), bits(S[key][b]), err_msg=str((c.name, key)))
+            continue
+        assert info is not None, c.name   # past the ladder: the step ran or its QP had no solution
+        assert got["rec"][0] == (0 if info[1] in (1, 2, -2) else 6), (c.name, got["rec"][0], info)
+        if want["rec"][0] != 0:   # a QP without a solution: the record holds the state, nothing else moves
+            np.testing.assert_array_equal(bits(got["rec"][4:11]), bits(x0[b]), err_msg=c.name)
+            np.testing.assert_array_equal(got["rec"][2], 0.0, err_msg=c.name)
+            assert np.all(got["rec"][[1, 3, 11, 12, 15]] == 0) and got["rec"][14] == info[1], (c.name, got["rec"])
+            for key in ("x", "Xw", "Uw", "y", "rho"):
+                np.testing.assert_array_equal(bits(got[key]), bits(S[key][b]), err_msg=str((c.name, key)))
+            failed += 1
+            continue
+        live += 1
+        for key in ("x", "Xw", "Uw"):
+            ok, worst = close(got[key], want[key], 1.0)
+            assert ok, (c.name, key, worst)
+        ok, worst = close(got["rho"], want["rho"], 0.0); assert ok, (c.name, "rho", worst)
+        ok, worst = close(got["y"], want["y"], np.abs(want["y"]).max()); assert ok, (c.name, "y", worst)
+    print("fleet ladder, solver", solver, "outcomes", sorted(seen), "live", live, "failed QPs", failed)
+    assert seen >= {0, 1, 2, 3, 4, 6} and live >= 3 and failed >= 1, (seen, live, failed)
+
+
 def test_fleet_flights_match_oracle(gpu_ctx):
     """The same 24 landings flown free-running on the fleet and by the oracle's
     closed loop (mc_oracle.closed_loop_landing = monte_carlo.py:401-583):

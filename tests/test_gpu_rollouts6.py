@@ -9,7 +9,10 @@ warm-start controls U, OSQP's persistent scaled y and rho, the record), so the
 inputs are identical: ADMM iterations, status, outcome and step count exact;
 the forward-simulated X_pred, its GP means, the QP plan X, the new U, the next
 state, rho and the duals within the SURVEY 8c tolerance (1e-6 relative, unit
-floor; duals floored at max |y|)."""
+floor; duals floored at max |y|).
+
+No rollout here is flown to its end: the termination ladder, a QP without a solution, the
+record at termination and rows frozen beside flying ones are test_gpu_rollouts6_termination.py."""
 import numpy as np
 import pytest
 
