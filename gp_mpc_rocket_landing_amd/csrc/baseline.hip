@@ -311,29 +311,26 @@ extern "C" int gpmpc_baseline_fly(gpmpc_ctx *ctx, const gpmpc_baseline_config *c
   const size_t nref = kind == GPMPC_BASELINE_OPEN_LOOP ? (size_t)cfg->n_ref : 0;
   const size_t nK = kind == GPMPC_BASELINE_LQR ? B : 0;
   const size_t ntr = a.thrust_on ? (size_t)cfg->thrust_rows : 0, nwr = a.wind_kind ? (size_t)cfg->wind_rows : 0;
-  const size_t bytes = Stage::pad(8 * B * BL_NX) + Stage::pad(8 * nK * BL_NU * BL_NX) + Stage::pad(8 * nK * BL_NU) +
-                       Stage::pad(8 * nref * BL_NU) + Stage::pad(8 * ntr * 4) + Stage::pad(8 * nwr * 3) +
-                       Stage::pad(4 * (a.wind_kind ? T : 0)) + Stage::pad(8 * (a.drag ? B : 0)) +
-                       Stage::pad(8 * (sim ? B * T * 4 : 0)) + Stage::pad(8 * B * GPMPC_REC_LEN) + Stage::pad(4 * B);
-  Stage sg(s, bytes);
   DevBuf logbuf;
-  if (!sg.ok() || (a.log && logbuf.alloc(s, sizeof(double) * B * T * BL_ROW) != hipSuccess)) {
+  if (a.log && logbuf.alloc(s, sizeof(double) * B * T * BL_ROW) != hipSuccess) {
     gpmpc_set_error("baseline_fly: staging and log buffers: out of memory");
     return -1;
   }
-  a.x0 = sg.in(x0, B * BL_NX);
-  a.K = sg.in(K, nK * BL_NU * BL_NX);
-  a.uh = sg.in(u_hover, nK * BL_NU);
-  a.Uref = sg.in(U_ref, nref * BL_NU);
-  a.ttab = sg.in(thrust_table, ntr * 4);
-  a.wtab = sg.in(wind_table, nwr * 3);
-  a.wrow = sg.in(wind_step_rows, a.wind_kind ? T : 0);
-  a.cda = sg.in(drag_cda, a.drag ? B : 0);
-  a.noise = sg.in(noise, sim ? B * T * 4 : 0);
-  a.rec = sg.out(records, B * GPMPC_REC_LEN);
-  a.nsteps = sg.out(nsteps, B);
   a.logbuf = logbuf.as<double>();
-  GPMPC_HIP(sg.upload());
+  // a table the kind or the switches leave unread takes no room (count 0, or a null pointer)
+  Stage sg(s);
+  sg.in(&a.x0, x0, B * BL_NX);
+  sg.in(&a.K, K, nK * BL_NU * BL_NX);
+  sg.in(&a.uh, u_hover, nK * BL_NU);
+  sg.in(&a.Uref, U_ref, nref * BL_NU);
+  sg.in(&a.ttab, thrust_table, ntr * 4);
+  sg.in(&a.wtab, wind_table, nwr * 3);
+  sg.in(&a.wrow, wind_step_rows, a.wind_kind ? T : 0);
+  sg.in(&a.cda, drag_cda, a.drag ? B : 0);
+  sg.in(&a.noise, noise, sim ? B * T * 4 : 0);
+  sg.out(&a.rec, records, B * GPMPC_REC_LEN);
+  sg.out(&a.nsteps, nsteps, B);
+  if (int rc = sg.commit("baseline_fly")) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (kernel_ms) {
     GPMPC_HIP(hipEventCreate(&e0));

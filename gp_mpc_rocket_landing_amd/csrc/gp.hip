@@ -741,14 +741,11 @@ extern "C" int gpmpc_gp_predict(gpmpc_ctx *ctx, gpmpc_gp *gp, const double *Xq, 
   const GpCore &g = gp->core;
   DevBuf Ks;
   // the queries in one pinned upload, mean and variance in one read-back
-  const size_t P = p, bo = Stage::pad(8 * P * g.n_out);
-  Stage sg(s, Stage::pad(8 * P * g.d) + 2 * bo);
-  if (!sg.ok()) {
-    gpmpc_set_error("gp_predict: staging buffers: out of memory");
-    return -1;
-  }
-  double *dq = sg.in(Xq, P * g.d), *dmean = sg.out(mean, P * g.n_out), *dvar = sg.out(var, P * g.n_out);
-  GPMPC_HIP(sg.upload());
+  const size_t P = p;
+  Stage sg(s);
+  double *dq, *dmean, *dvar;
+  sg.in(&dq, Xq, P * g.d); sg.out(&dmean, mean, P * g.n_out); sg.out(&dvar, var, P * g.n_out);
+  if (int rc = sg.commit("gp_predict")) return rc;
   if (g.Wf.p && post_cs_env()) {
     // K* formed inside the column-stationary posterior (post.hip): no K* in HBM
     DevBuf qs, qn, part, meanT;
@@ -1269,14 +1266,11 @@ extern "C" int gpmpc_fitc_predict(gpmpc_ctx *ctx, gpmpc_fitc *gp, const double *
   GPMPC_HIP(hipSetDevice(ctx->device));
   const GpCore &g = gp->core;
   // the queries in one pinned upload, mean and variance in one read-back
-  const size_t P = p, bo = Stage::pad(8 * P * g.n_out);
-  Stage sg(ctx->stream, Stage::pad(8 * P * g.d) + 2 * bo);
-  if (!sg.ok()) {
-    gpmpc_set_error("fitc_predict: staging buffers: out of memory");
-    return -1;
-  }
-  double *dq = sg.in(Xq, P * g.d), *dmean = sg.out(mean, P * g.n_out), *dvar = sg.out(var, P * g.n_out);
-  GPMPC_HIP(sg.upload());
+  const size_t P = p;
+  Stage sg(ctx->stream);
+  double *dq, *dmean, *dvar;
+  sg.in(&dq, Xq, P * g.d); sg.out(&dmean, mean, P * g.n_out); sg.out(&dvar, var, P * g.n_out);
+  if (int rc = sg.commit("fitc_predict")) return rc;
   const int rc = fitc_posterior_dev(ctx, gp, dq, p, dmean, dvar);
   if (rc) return rc;
   GPMPC_HIP(sg.download());

@@ -290,18 +290,12 @@ extern "C" int gpmpc_hull_project(gpmpc_ctx *ctx, const double *V, const double 
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t nb = (size_t)B, sets = shared ? 1 : nb, kd = (size_t)kmax * d;
-  Stage sg(s, Stage::pad(8 * sets * kd) + (q ? Stage::pad(8 * sets * kmax) + Stage::pad(8 * nb) : 0) +
-                  (nv ? Stage::pad(4 * nb) : 0) + 2 * Stage::pad(8 * nb * d) + Stage::pad(8 * nb * kmax) +
-                  2 * Stage::pad(8 * nb) + 2 * Stage::pad(4 * nb));
-  if (!sg.ok()) {
-    gpmpc_set_error("hull_project: staging buffers: out of memory");
-    return -1;
-  }
+  Stage sg(s);
   HullArgs a{};
-  a.V = sg.in(V, sets * kd);
-  a.q = q ? sg.in(q, sets * kmax) : nullptr;
-  a.nv = nv ? sg.in(nv, nb) : nullptr;
-  a.X = sg.in(X, nb * d);
+  sg.in(&a.V, V, sets * kd);
+  sg.in(&a.q, q, sets * kmax);  // null without q
+  sg.in(&a.nv, nv, nb);         // null without nv
+  sg.in(&a.X, X, nb * d);
   a.gidx = nullptr;
   a.B = B;
   a.kmax = kmax;
@@ -309,14 +303,14 @@ extern "C" int gpmpc_hull_project(gpmpc_ctx *ctx, const double *V, const double 
   a.shared = shared;
   a.tol = tol;
   a.max_iter = max_iter;
-  a.lambda = sg.out(lambda, nb * kmax);
-  a.proj = sg.out(proj, nb * d);
-  a.dist = sg.out(dist, nb);
-  a.gap = sg.out(gap, nb);
-  a.qhull = q ? sg.out(qhull, nb) : nullptr;
-  a.iters = sg.out(iters, nb);
-  a.status = sg.out(status, nb);
-  GPMPC_HIP(sg.upload());
+  sg.out(&a.lambda, lambda, nb * kmax);
+  sg.out(&a.proj, proj, nb * d);
+  sg.out(&a.dist, dist, nb);
+  sg.out(&a.gap, gap, nb);
+  sg.out(&a.qhull, q ? qhull : nullptr, nb);  // (written when a.q is given)
+  sg.out(&a.iters, iters, nb);
+  sg.out(&a.status, status, nb);
+  if (int rc = sg.commit("hull_project")) return rc;
   GPMPC_HIP(launch_hull(s, a));
   GPMPC_HIP(sg.download());
   return 0;

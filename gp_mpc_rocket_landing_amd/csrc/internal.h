@@ -7,6 +7,7 @@
 #include <string>
 #include <utility>
 #include "../../include/gpmpc.h"
+#include "stage.h"
 
 struct gpmpc_ctx {
   int device = 0;
@@ -100,72 +101,42 @@ struct DevBuf {
 // read back with ONE copy (a pageable hipMemcpyAsync costs 10-30 us of host time; a
 // single-landing QP solve made 14 of them).  The arenas are per stream (= per
 // context; device side = gpmpc_scratch slot 7), grown after the stream drains, and
-// valid until the next Stage on the stream.  Order of use: in() for pure inputs,
-// inout() for buffers both read and written back, then out(); upload() after the
-// last in/inout, download() after the last kernel (it synchronises the stream).
+// valid until the next Stage on the stream.  Order of use: declare every buffer once
+// (stage.h: in(&dev, host, count), then inout(), then out()); commit(what) sizes both
+// arenas from the declarations, packs the inputs, writes every declared device pointer
+// and uploads; download() after the last kernel (it synchronises the stream).
 char *gpmpc_stage_host(hipStream_t s, size_t bytes);
 void gpmpc_qp_cache_release(hipStream_t s);  // qp.hip: the stream's kept QP pattern
-struct Stage {
-  struct Back { void *dst; size_t off, bytes; };
+struct Stage : StageLayout {
   hipStream_t s;
   char *h = nullptr, *d = nullptr;
-  size_t off = 0, in_end = 0, back_lo = (size_t)-1, cap = 0;
-  bool bad = false;  // a buffer past the arena (the caller's byte count was short): upload() refuses
-  Back backs[24];
-  int nback = 0;
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-  // bytes: the sum of pad(size) over every buffer the call stages
-  Stage(hipStream_t st, size_t bytes) : s(st), cap(bytes) {
-    h = gpmpc_stage_host(s, bytes);
-    d = (char *)gpmpc_scratch(s, 7, bytes);
-  }
-  bool fits(size_t b) {
-    if (off + pad(b) <= cap) return true;
-    bad = true;
-    return false;
-  }
-  bool ok() const { return h && d; }
-  template <class T> T *in(const T *src, size_t n) {
-    const size_t b = sizeof(T) * n;
-    if (!fits(b)) return (T *)d;
-    if (b) memcpy(h + off, src, b);
-    T *r = (T *)(d + off);
-    off += pad(b);
-    return r;
-  }
-  template <class T> T *inout(T *src, size_t n) {
-    const size_t o = off;
-    T *r = in(src, n);
-    if (!bad) back(src, o, sizeof(T) * n);
-    return r;
-  }
-  template <class T> T *out(T *dst, size_t n) {
-    const size_t o = off;
-    if (!fits(sizeof(T) * n)) return (T *)d;
-    off += pad(sizeof(T) * n);
-    back(dst, o, sizeof(T) * n);
-    return (T *)(d + o);
-  }
-  void back(void *dst, size_t o, size_t b) {
-    if (o < back_lo) back_lo = o;
-    if (nback < (int)(sizeof(backs) / sizeof(backs[0]))) backs[nback] = Back{dst, o, b};
-    ++nback;  // (past the table: download() refuses)
-  }
-  hipError_t upload() {
-    if (bad) return hipErrorInvalidValue;
-    in_end = off;
-    return off ? hipMemcpyAsync(d, h, off, hipMemcpyHostToDevice, s) : hipSuccess;
+  explicit Stage(hipStream_t st) : s(st) {}
+  // 0, or -1 with the error set and no declared pointer written
+  int commit(const char *what) {
+    if (refused) {
+      gpmpc_set_error("%s: staging buffers: %s", what, refused);
+      return -1;
+    }
+    h = gpmpc_stage_host(s, total);
+    d = (char *)gpmpc_scratch(s, 7, total);
+    if (!h || !d) {
+      gpmpc_set_error("%s: staging buffers: out of memory", what);
+      return -1;
+    }
+    pack(h);
+    bind(d);
+    // the whole arena goes up, outputs included (trimming it to the inputs is a speed change of its own)
+    if (total) GPMPC_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, s));
+    return 0;
   }
   hipError_t download() {
-    if (bad || nback > (int)(sizeof(backs) / sizeof(backs[0]))) return hipErrorInvalidValue;
-    if (nback) {
-      hipError_t e = hipMemcpyAsync(h + back_lo, d + back_lo, off - back_lo, hipMemcpyDeviceToHost, s);
+    if (back_lo != kNone) {
+      hipError_t e = hipMemcpyAsync(h + back_lo, d + back_lo, total - back_lo, hipMemcpyDeviceToHost, s);
       if (e != hipSuccess) return e;
     }
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
-    for (int i = 0; i < nback; ++i)
-      if (backs[i].bytes) memcpy(backs[i].dst, h + backs[i].off, backs[i].bytes);
+    fetch(h);
     return hipSuccess;
   }
 };

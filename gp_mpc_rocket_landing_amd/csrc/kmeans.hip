@@ -249,20 +249,17 @@ extern "C" int gpmpc_kmeans_lloyd(gpmpc_ctx *ctx, const double *X, int n, int d,
   DevBuf dA, dB;  // the code books between the first and the last
   if (iters > 1) GPMPC_HIP(dA.alloc(s, sizeof(double) * kd));
   if (iters > 2) GPMPC_HIP(dB.alloc(s, sizeof(double) * kd));
-  const size_t bytes = Stage::pad(8 * nd) + Stage::pad(8 * kd) + Stage::pad(8 * (ni + 1)) + Stage::pad(8) +
-                       Stage::pad(4) + Stage::pad(4 * ni) + Stage::pad(8 * kd) + Stage::pad(4 * (size_t)n);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("kmeans_lloyd: staging buffers: out of memory");
-    return -1;
-  }
-  const double *dX = sg.in(X, nd), *dC0 = sg.in(C0, kd);
-  double *dcmax = sg.in(cmax.data(), ni + 1);
-  double *dmargin = sg.inout(min_margin, 1);
-  int *dunsafe = sg.inout(unsafe, 1), *dempty = sg.inout(empty_per_iter, ni);
-  double *dC = sg.out(C_out, kd);
-  int *dlabel = sg.out(labels_out, (size_t)n);
-  GPMPC_HIP(sg.upload());
+  Stage sg(s);
+  const double *dX, *dC0;
+  double *dcmax, *dmargin, *dC;
+  int *dunsafe, *dempty, *dlabel;
+  sg.in(&dX, X, nd); sg.in(&dC0, C0, kd);
+  sg.in(&dcmax, cmax.data(), ni + 1);  // (cmax lives until the commit packs it)
+  sg.inout(&dmargin, min_margin, 1);
+  sg.inout(&dunsafe, unsafe, 1); sg.inout(&dempty, empty_per_iter, ni);
+  sg.out(&dC, C_out, kd);
+  sg.out(&dlabel, labels_out, (size_t)n);
+  if (int rc = sg.commit("kmeans_lloyd")) return rc;
   const double tau = gpmpc_kmeans_tau(d);
   const dim3 ga((unsigned)(((int64_t)n + KM_OBS - 1) / KM_OBS));
   const dim3 gu((unsigned)(((int64_t)k + KM_UPD_THREADS / 64 - 1) / (KM_UPD_THREADS / 64)));

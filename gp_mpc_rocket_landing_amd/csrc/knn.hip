@@ -574,18 +574,16 @@ extern "C" int gpmpc_knn_query(gpmpc_knn *set, int order, const double *Xq, int 
   GPMPC_HIP(hipSetDevice(set->ctx->device));
   hipStream_t s = set->ctx->stream;
   const size_t nb = (size_t)B, d = (size_t)set->d;
-  Stage sg(s, Stage::pad(8 * nb * d) + (avail_fuel ? Stage::pad(8 * nb) : 0) + Stage::pad(4 * nb * k) +
-                  Stage::pad(8 * nb * k) + 2 * Stage::pad(4 * nb));
-  if (!sg.ok()) {
-    gpmpc_set_error("knn_query: staging buffers: out of memory");
-    return -1;
-  }
-  const double *dXq = sg.in(Xq, nb * d);
-  const double *dav = avail_fuel ? sg.in(avail_fuel, nb) : nullptr;
-  int *didx = sg.out(idx, nb * k);
-  double *ddist = sg.out(dist, nb * k);
-  int *dball = sg.out(n_ball, nb), *dfeas = sg.out(n_feasible, nb);
-  GPMPC_HIP(sg.upload());
+  Stage sg(s);
+  const double *dXq, *dav;  // dav null without avail_fuel
+  int *didx, *dball, *dfeas;
+  double *ddist;
+  sg.in(&dXq, Xq, nb * d);
+  sg.in(&dav, avail_fuel, nb);
+  sg.out(&didx, idx, nb * k);
+  sg.out(&ddist, dist, nb * k);
+  sg.out(&dball, n_ball, nb); sg.out(&dfeas, n_feasible, nb);
+  if (int rc = sg.commit("knn_query")) return rc;
   KnnFinal f;
   if (int rc = knn_search(set, order, dXq, B, dav, radius, f)) return rc;
   hipLaunchKernelGGL(k_knn_emit, dim3((unsigned)B), dim3(64), 0, s, f.s, f.i, f.cnt, set->n, k, didx, ddist, dball,
@@ -609,17 +607,15 @@ extern "C" int gpmpc_knn_interp(gpmpc_knn *set, int order, const double *Xq, int
   GPMPC_HIP(hipSetDevice(set->ctx->device));
   hipStream_t s = set->ctx->stream;
   const size_t nb = (size_t)B, d = (size_t)set->d;
-  Stage sg(s, Stage::pad(8 * nb * d) + (avail_fuel ? Stage::pad(8 * nb) : 0) + Stage::pad(8 * nb) +
-                  Stage::pad(4 * nb));
-  if (!sg.ok()) {
-    gpmpc_set_error("knn_interp: staging buffers: out of memory");
-    return -1;
-  }
-  const double *dXq = sg.in(Xq, nb * d);
-  const double *dav = avail_fuel ? sg.in(avail_fuel, nb) : nullptr;
-  double *dq = sg.out(q_out, nb);
-  int *dk = sg.out(k_used, nb);
-  GPMPC_HIP(sg.upload());
+  Stage sg(s);
+  const double *dXq, *dav;  // dav null without avail_fuel
+  double *dq;
+  int *dk;
+  sg.in(&dXq, Xq, nb * d);
+  sg.in(&dav, avail_fuel, nb);
+  sg.out(&dq, q_out, nb);
+  sg.out(&dk, k_used, nb);
+  if (int rc = sg.commit("knn_interp")) return rc;
   KnnFinal f;
   if (int rc = knn_search(set, order, dXq, B, dav, radius, f)) return rc;
   hipLaunchKernelGGL(k_knn_interp, dim3((unsigned)B), dim3(64), 0, s, f.s, f.i, f.cnt, set->q.as<double>(), k_base,
@@ -679,22 +675,12 @@ extern "C" int gpmpc_knn_hull(gpmpc_knn *set, int order, const double *Xq, const
   hipStream_t s = set->ctx->stream;
   const size_t nb = (size_t)B, d = (size_t)set->d, dp = (size_t)set->dp, km = (size_t)k_max;
   const bool with_q = set->q.p && qhull;
-  Stage sg(s, Stage::pad(8 * nb * d) + 2 * Stage::pad(8 * nb * dp) + (avail_fuel ? Stage::pad(8 * nb) : 0) +
-                  5 * Stage::pad(4 * nb) + Stage::pad(4 * nb * km) + Stage::pad(8 * nb * km) + 3 * Stage::pad(8 * nb));
-  if (!sg.ok()) {
-    gpmpc_set_error("knn_hull: staging buffers: out of memory");
-    return -1;
-  }
-  const double *dXq = sg.in(Xq, nb * d);
-  const double *dXp = sg.in(Xp, nb * dp);
-  const double *dav = avail_fuel ? sg.in(avail_fuel, nb) : nullptr;
   DevBuf nvbuf;  // the vertex counts stay on the device
   GPMPC_HIP(nvbuf.alloc(s, sizeof(int) * nb));
   int *dnv = nvbuf.as<int>();
   HullArgs a{};
   a.V = set->P.as<double>();
   a.q = with_q ? set->q.as<double>() : nullptr;
-  a.X = dXp;
   a.nv = dnv;
   a.B = B;
   a.kmax = k_max;
@@ -702,17 +688,23 @@ extern "C" int gpmpc_knn_hull(gpmpc_knn *set, int order, const double *Xq, const
   a.shared = 0;
   a.tol = tol;
   a.max_iter = max_iter;
-  int *dused = sg.out(k_used, nb);
-  int *didx = sg.out(idx, nb * km);
+  Stage sg(s);
+  const double *dXq, *dav;  // dav null without avail_fuel
+  int *dused, *didx;
+  sg.in(&dXq, Xq, nb * d);
+  sg.in(&a.X, Xp, nb * dp);
+  sg.in(&dav, avail_fuel, nb);
+  sg.out(&dused, k_used, nb);
+  sg.out(&didx, idx, nb * km);
+  sg.out(&a.lambda, lambda, nb * km);
+  sg.out(&a.proj, proj, nb * dp);
+  sg.out(&a.dist, dist, nb);
+  sg.out(&a.gap, gap, nb);
+  sg.out(&a.qhull, with_q ? qhull : nullptr, nb);  // (written when a.q is given)
+  sg.out(&a.iters, iters, nb);
+  sg.out(&a.status, status, nb);
+  if (int rc = sg.commit("knn_hull")) return rc;
   a.gidx = didx;
-  a.lambda = sg.out(lambda, nb * km);
-  a.proj = sg.out(proj, nb * dp);
-  a.dist = sg.out(dist, nb);
-  a.gap = sg.out(gap, nb);
-  a.qhull = with_q ? sg.out(qhull, nb) : nullptr;
-  a.iters = sg.out(iters, nb);
-  a.status = sg.out(status, nb);
-  GPMPC_HIP(sg.upload());
   KnnFinal f;
   if (int rc = knn_search(set, order, dXq, B, dav, radius, f)) return rc;
   hipLaunchKernelGGL(k_knn_hull_prep, dim3((unsigned)B), dim3(64), 0, s, f.i, f.cnt, set->n, k_base, k_min, k_max,

@@ -224,23 +224,19 @@ extern "C" int gpmpc_qp_solve_batched(gpmpc_ctx *ctx, int batch, int n, int m, i
   for (int64_t r = 0; fleet && r < (int64_t)batch * m; ++r)
     if (r % m < QP_FLEET_MD && l[r] != u[r]) fleet = false;
   // every input in one pinned upload, every output in one read-back
-  const size_t B = batch, dn = 8 * B * n, dm = 8 * B * m;
-  const size_t bytes = Stage::pad(8 * B * nnz) + 2 * Stage::pad(dn) + 2 * Stage::pad(dm) +
-                       (x_ws ? Stage::pad(dn) : 0) + Stage::pad(8 * B) + Stage::pad(dm) + Stage::pad(dn) +
-                       Stage::pad(dm) + 2 * Stage::pad(4 * B) + Stage::pad(8 * B);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("qp: staging buffers: out of memory");
-    return -1;
-  }
-  const double *dA = sg.in(Aval, B * nnz), *dP = sg.in(Pdiag, B * n), *dq = sg.in(q, B * n);
-  const double *dl = sg.in(l, B * m), *du = sg.in(u, B * m);
-  const double *dx0 = x_ws ? sg.in(x_ws, B * n) : nullptr;
-  double *drho = sg.inout(rho, B), *dy0 = sg.inout(y_scaled, B * m);
-  double *dxo = sg.out(x, B * n), *dyo = sg.out(y, B * m);
-  int *dit = sg.out(iters, B), *dst = sg.out(status, B);
-  double *dob = sg.out(obj, B);
-  GPMPC_HIP(sg.upload());
+  const size_t B = batch;
+  Stage sg(s);
+  const double *dA, *dP, *dq, *dl, *du, *dx0;  // dx0 null without a warm start
+  double *drho, *dy0, *dxo, *dyo, *dob;
+  int *dit, *dst;
+  sg.in(&dA, Aval, B * nnz); sg.in(&dP, Pdiag, B * n); sg.in(&dq, q, B * n);
+  sg.in(&dl, l, B * m); sg.in(&du, u, B * m);
+  sg.in(&dx0, x_ws, B * n);
+  sg.inout(&drho, rho, B); sg.inout(&dy0, y_scaled, B * m);
+  sg.out(&dxo, x, B * n); sg.out(&dyo, y, B * m);
+  sg.out(&dit, iters, B); sg.out(&dst, status, B);
+  sg.out(&dob, obj, B);
+  if (int rc = sg.commit("qp")) return rc;
   // GPMPC_QP_STAMPS=1: problem 0's phase cycles (s_memtime) to stderr, a diagnostic
   static const int stamp = gpmpc_env_int("GPMPC_QP_STAMPS", 0);
   DevBuf dts;

@@ -318,24 +318,18 @@ extern "C" int gpmpc_safety_filter(gpmpc_ctx *ctx, const double *rocket, const g
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t B = batch;
-  const size_t bytes = Stage::pad(8 * SF_NTAB) + Stage::pad(8 * B * R6_NX) + 2 * Stage::pad(8 * B * R6_NU) +
-                       2 * Stage::pad(8 * B) + 3 * Stage::pad(4 * B);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("safety_filter: staging buffers: out of memory");
-    return -1;
-  }
+  Stage sg(s);
   a.T = 0;
-  a.tab = sg.in(cfg->K, SF_NTAB);
-  a.x = sg.in(x, B * R6_NX);
-  a.u_nom = sg.in(u_nom, B * R6_NU);
-  a.u_safe = sg.out(u_safe, B * R6_NU);
-  a.margin = sg.out(margin, B);
-  a.value = sg.out(backup_value, B);
-  a.flags = sg.out(flags, B);
-  a.mask = sg.out(viol_mask, B);
-  a.iters = sg.out(iters, B);
-  GPMPC_HIP(sg.upload());
+  sg.in(&a.tab, cfg->K, SF_NTAB);
+  sg.in(&a.x, x, B * R6_NX);
+  sg.in(&a.u_nom, u_nom, B * R6_NU);
+  sg.out(&a.u_safe, u_safe, B * R6_NU);
+  sg.out(&a.margin, margin, B);
+  sg.out(&a.value, backup_value, B);
+  sg.out(&a.flags, flags, B);
+  sg.out(&a.mask, viol_mask, B);
+  sg.out(&a.iters, iters, B);
+  if (int rc = sg.commit("safety_filter")) return rc;
   hipLaunchKernelGGL(k_safety<false>, dim3((batch + SF_QUADS - 1) / SF_QUADS), dim3(SF_WAVE), 0, s, a);
   GPMPC_HIP(hipGetLastError());
   GPMPC_HIP(sg.download());
@@ -351,23 +345,17 @@ extern "C" int gpmpc_safety_simulate(gpmpc_ctx *ctx, const double *rocket, const
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t B = batch, BT = B * (size_t)T;
-  const size_t bytes = Stage::pad(8 * SF_NTAB) + Stage::pad(8 * B * R6_NX) + 2 * Stage::pad(8 * BT * R6_NU) +
-                       Stage::pad(8 * B * (T + 1) * R6_NX) + Stage::pad(8 * BT) + 2 * Stage::pad(4 * BT);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("safety_simulate: staging buffers: out of memory");
-    return -1;
-  }
+  Stage sg(s);
   a.T = T;
-  a.tab = sg.in(cfg->K, SF_NTAB);
-  a.x = sg.in(x0, B * R6_NX);
-  a.u_nom = sg.in(U_nom, BT * R6_NU);
-  a.X = sg.out(X, B * (T + 1) * R6_NX);
-  a.u_safe = sg.out(U, BT * R6_NU);
-  a.margin = sg.out(margin, BT);
-  a.flags = sg.out(flags, BT);
-  a.iters = sg.out(iters, BT);
-  GPMPC_HIP(sg.upload());
+  sg.in(&a.tab, cfg->K, SF_NTAB);
+  sg.in(&a.x, x0, B * R6_NX);
+  sg.in(&a.u_nom, U_nom, BT * R6_NU);
+  sg.out(&a.X, X, B * (T + 1) * R6_NX);
+  sg.out(&a.u_safe, U, BT * R6_NU);
+  sg.out(&a.margin, margin, BT);
+  sg.out(&a.flags, flags, BT);
+  sg.out(&a.iters, iters, BT);
+  if (int rc = sg.commit("safety_simulate")) return rc;
   hipLaunchKernelGGL(k_safety<true>, dim3((batch + SF_QUADS - 1) / SF_QUADS), dim3(SF_WAVE), 0, s, a);
   GPMPC_HIP(hipGetLastError());
   GPMPC_HIP(sg.download());

@@ -212,24 +212,17 @@ extern "C" int gpmpc_tube_linear(gpmpc_ctx *ctx, const double *rocket, int batch
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t B = batch, BN = B * (size_t)N, nw = w_mode == 0 ? 0 : w_mode == 1 ? R6_NX : BN * R6_NX;
-  const size_t bytes = Stage::pad(8 * B * (N + 1) * R6_NX) + Stage::pad(8 * BN * R6_NU) + Stage::pad(8 * nw) +
-                       Stage::pad(8 * R6_NU * R6_NX) + Stage::pad(8 * B * (N + 1) * R6_NX) +
-                       (A_out ? Stage::pad(8 * BN * R6_NX * R6_NX) : 0) + (B_out ? Stage::pad(8 * BN * R6_NX * R6_NU) : 0);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("tube_linear: staging buffers: out of memory");
-    return -1;
-  }
+  Stage sg(s);
   a.B = batch; a.N = N; a.w_mode = w_mode; a.have_K = K ? 1 : 0;
   a.dt = dt; a.eps = eps; a.w_max = w_max;
-  a.X = sg.in(X_nom, B * (N + 1) * R6_NX);
-  a.U = sg.in(U_nom, BN * R6_NU);
-  a.w = nw ? sg.in(w, nw) : nullptr;
-  a.K = K ? sg.in(K, (size_t)R6_NU * R6_NX) : nullptr;
-  a.tubes = sg.out(tubes, B * (N + 1) * R6_NX);
-  a.A_out = A_out ? sg.out(A_out, BN * R6_NX * R6_NX) : nullptr;
-  a.B_out = B_out ? sg.out(B_out, BN * R6_NX * R6_NU) : nullptr;
-  GPMPC_HIP(sg.upload());
+  sg.in(&a.X, X_nom, B * (N + 1) * R6_NX);
+  sg.in(&a.U, U_nom, BN * R6_NU);
+  sg.in(&a.w, nw ? w : nullptr, nw);  // null where no bound is read (w_mode 0, or no steps)
+  sg.in(&a.K, K, (size_t)R6_NU * R6_NX);  // K, A_out, B_out: null where the caller gives none
+  sg.out(&a.tubes, tubes, B * (N + 1) * R6_NX);
+  sg.out(&a.A_out, A_out, BN * R6_NX * R6_NX);
+  sg.out(&a.B_out, B_out, BN * R6_NX * R6_NU);
+  if (int rc = sg.commit("tube_linear")) return rc;
   hipLaunchKernelGGL(k_tube_linear, dim3(batch), dim3(TB_T), 0, s, a);
   GPMPC_HIP(hipGetLastError());
   GPMPC_HIP(sg.download());
@@ -270,18 +263,13 @@ extern "C" int gpmpc_tube_mc(gpmpc_ctx *ctx, const double *rocket, int batch, in
   GPMPC_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t B = batch, BN = B * (size_t)N, S = n_samples;
-  const size_t bytes = 2 * Stage::pad(8 * B * (N + 1) * R6_NX) + Stage::pad(8 * BN * R6_NU) + Stage::pad(8 * BN * S * R6_NX);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("tube_mc: staging buffers: out of memory");
-    return -1;
-  }
+  Stage sg(s);
   a.B = batch; a.N = N; a.S = n_samples; a.dt = dt;
-  a.X = sg.in(X_nom, B * (N + 1) * R6_NX);
-  a.U = sg.in(U_nom, BN * R6_NU);
-  a.noise = sg.in(noise, BN * S * R6_NX);
-  a.tubes = sg.out(tubes, B * (N + 1) * R6_NX);
-  GPMPC_HIP(sg.upload());
+  sg.in(&a.X, X_nom, B * (N + 1) * R6_NX);
+  sg.in(&a.U, U_nom, BN * R6_NU);
+  sg.in(&a.noise, noise, BN * S * R6_NX);
+  sg.out(&a.tubes, tubes, B * (N + 1) * R6_NX);
+  if (int rc = sg.commit("tube_mc")) return rc;
   if (n_samples <= 128)
     hipLaunchKernelGGL(k_tube_mc<128>, dim3(batch), dim3(128), 0, s, a);
   else if (n_samples <= 256)

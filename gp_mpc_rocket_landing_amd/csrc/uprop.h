@@ -188,18 +188,20 @@ static inline int up_posterior(gpmpc_ctx *ctx, void *gp, int exact, int d, const
 }
 
 // what every propagation call stages: x0 (B x n), U (B x N x 3) and S0 (B x n x n, or null)
-// up, means (B x (N+1) x n) and covs (B x (N+1) x n x n) back.  bytes(): their share of the
-// Stage's size; the constructor lays them out and holds the device pointers.  A caller with
-// inputs of its own stages them first, with outputs of its own after (Stage's order of use).
+// up, means (B x (N+1) x n) and covs (B x (N+1) x n x n) back.  The constructor declares them
+// and the Stage's commit fills in the device pointers (so an UpIo stays where it was made).  A
+// caller with inputs of its own declares them first, with outputs of its own after (Stage's
+// order of use).
 struct UpIo {
   const double *x0, *U, *S0;
   double *means, *covs;
-  static size_t bytes(size_t B, size_t N, size_t n, bool s0) {
-    return Stage::pad(8 * B * n) + Stage::pad(8 * B * N * 3) + (s0 ? Stage::pad(8 * B * n * n) : 0) +
-           Stage::pad(8 * B * (N + 1) * n) + Stage::pad(8 * B * (N + 1) * n * n);
-  }
   UpIo(Stage &sg, size_t B, size_t N, size_t n, const double *hx0, const double *hU, const double *hS0,
-       double *hmeans, double *hcovs)
-      : x0(sg.in(hx0, B * n)), U(sg.in(hU, B * N * 3)), S0(hS0 ? sg.in(hS0, B * n * n) : nullptr),
-        means(sg.out(hmeans, B * (N + 1) * n)), covs(sg.out(hcovs, B * (N + 1) * n * n)) {}
+       double *hmeans, double *hcovs) {
+    sg.in(&x0, hx0, B * n);
+    sg.in(&U, hU, B * N * 3);
+    sg.in(&S0, hS0, B * n * n);
+    sg.out(&means, hmeans, B * (N + 1) * n);
+    sg.out(&covs, hcovs, B * (N + 1) * n * n);
+  }
+  UpIo(const UpIo &) = delete;
 };

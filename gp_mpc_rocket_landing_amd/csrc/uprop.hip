@@ -225,13 +225,9 @@ extern "C" int gpmpc_uprop3_linear(gpmpc_ctx *ctx, gpmpc_gp *gp, int batch, int 
   GPMPC_HIP(dA.alloc(s, sizeof(double) * (P * NX * NX + 1)));
   GPMPC_HIP(dq.alloc(s, sizeof(double) * (P * NX + 1)));
   // inputs in one pinned upload, means and covariances in one read-back
-  Stage sg(s, UpIo::bytes(B, N, NX, S0));
-  if (!sg.ok()) {
-    gpmpc_set_error("uprop3_linear: staging buffers: out of memory");
-    return -1;
-  }
-  const UpIo io(sg, B, N, NX, x0, U, S0, means, covs);
-  GPMPC_HIP(sg.upload());
+  Stage sg(s);
+  UpIo io(sg, B, N, NX, x0, U, S0, means, covs);
+  if (int rc = sg.commit("uprop3_linear")) return rc;
   hipLaunchKernelGGL(k_uprop3_means, dim3(batch), dim3(256), 0, s, g, N, dt, alpha, g3[0], g3[1], g3[2], io.x0, io.U,
                      dQ.as<double>(), dA.as<double>(), io.means);
   GPMPC_HIP(hipGetLastError());
@@ -371,13 +367,9 @@ extern "C" int gpmpc_uprop6_linear(gpmpc_ctx *ctx, void *gp_v, void *gp_w, int e
   GPMPC_HIP(dA.alloc(s, sizeof(double) * (P * R6_NX * R6_NX + 1)));
   GPMPC_HIP(dq.alloc(s, sizeof(double) * (P * R6_NX + 1)));
   // inputs in one pinned upload, means and covariances in one read-back
-  Stage sg(s, UpIo::bytes(B, N, R6_NX, S0));
-  if (!sg.ok()) {
-    gpmpc_set_error("uprop6_linear: staging buffers: out of memory");
-    return -1;
-  }
-  const UpIo io(sg, B, N, R6_NX, x0, U, S0, means, covs);
-  GPMPC_HIP(sg.upload());
+  Stage sg(s);
+  UpIo io(sg, B, N, R6_NX, x0, U, S0, means, covs);
+  if (int rc = sg.commit("uprop6_linear")) return rc;
   hipLaunchKernelGGL(k_uprop6_means, dim3(batch), dim3(256), 0, s, gv, gw, rk, N, dt, io.x0, io.U, dQv.as<double>(),
                      dQw.as<double>(), dA.as<double>(), io.means);
   GPMPC_HIP(hipGetLastError());

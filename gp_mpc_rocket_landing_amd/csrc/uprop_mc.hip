@@ -179,13 +179,6 @@ static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void 
   hipStream_t s = ctx->stream;
   // inputs in one pinned upload; means, covariances (and the paths, when asked for) in one read-back
   const size_t npath = B * NP * S * n;
-  const size_t bytes = UpIo::bytes(B, N, n, S0) + Stage::pad(8 * P * n) + Stage::pad(8 * B * N * S * G * 3) +
-                       (particles ? Stage::pad(8 * npath) : 0);
-  Stage sg(s, bytes);
-  if (!sg.ok()) {
-    gpmpc_set_error("%s: staging buffers: out of memory", what);
-    return -1;
-  }
   DevBuf paths, dQv, dQw, mv, vv, mw, vw;
   GPMPC_HIP(dQv.alloc(s, sizeof(double) * (P * DV + 1)));
   for (DevBuf *d : {&mv, &vv}) GPMPC_HIP(d->alloc(s, sizeof(double) * P * 3));
@@ -194,15 +187,18 @@ static int mc_run(gpmpc_ctx *ctx, McArgs &a, const char *what, void *gp_v, void 
     for (DevBuf *d : {&mw, &vw}) GPMPC_HIP(d->alloc(s, sizeof(double) * P * 3));
   }
   if (!particles) GPMPC_HIP(paths.alloc(s, sizeof(double) * npath));
-  a.particles0 = sg.in(particles0, P * n);
-  a.normals = sg.in(normals, B * N * S * G * 3);
-  const UpIo io(sg, B, N, n, x0, U, S0, means, covs);
-  a.U = io.U;
-  a.paths = particles ? sg.out(particles, npath) : paths.as<double>();
+  Stage sg(s);
+  sg.in(&a.particles0, particles0, P * n);
+  sg.in(&a.normals, normals, B * N * S * G * 3);
+  UpIo io(sg, B, N, n, x0, U, S0, means, covs);
+  // the paths: read back when the caller asks for them, else a pooled temporary
+  if (particles) sg.out(&a.paths, particles, npath);
+  else a.paths = paths.as<double>();
   a.B = batch; a.N = N; a.S = n_samples;
   a.Qv = dQv.as<double>(); a.Qw = dQw.as<double>();
   a.mv = mv.as<double>(); a.vv = vv.as<double>(); a.mw = mw.as<double>(); a.vw = vw.as<double>();
-  GPMPC_HIP(sg.upload());
+  if (int rc = sg.commit(what)) return rc;
+  a.U = io.U;
   const dim3 grid((unsigned)((P + MC_T - 1) / MC_T));
   for (int k = -1; k < N; ++k) {
     if (k >= 0) {

@@ -368,15 +368,11 @@ static int ut_run(gpmpc_ctx *ctx, UtArgs &a, const char *what, int batch, int N,
   hipStream_t s = ctx->stream;
   const size_t B = batch;
   // inputs in one pinned upload; means, covariances and info in one read-back
-  Stage sg(s, UpIo::bytes(B, N, n, S0) + Stage::pad(4 * B));
-  if (!sg.ok()) {
-    gpmpc_set_error("%s: staging buffers: out of memory", what);
-    return -1;
-  }
-  const UpIo io(sg, B, N, n, x0, U, S0, means, covs);
+  Stage sg(s);
+  UpIo io(sg, B, N, n, x0, U, S0, means, covs);
+  sg.out(&a.info, info, B);
+  if (int rc = sg.commit(what)) return rc;
   a.x0 = io.x0; a.U = io.U; a.S0 = io.S0; a.means = io.means; a.covs = io.covs;
-  a.info = sg.out(info, B);
-  GPMPC_HIP(sg.upload());
   hipLaunchKernelGGL(k_uprop_ut<MODEL>, dim3(batch), dim3(256), sizeof(double) * (size_t)rows, s, a);
   GPMPC_HIP(hipGetLastError());
   GPMPC_HIP(sg.download());

@@ -133,6 +133,27 @@ def test_a_wave_with_lanes_that_run_to_max_steps_beside_early_finishers(g):
     assert all(r.failure_reason == "Exceeded 5.5s" for r in res if r.outcome.value == 5)
 
 
+def test_records_without_the_log(gpu_ctx, g):
+    """log = 0: no log buffer on either side.  The records of the first two short_lqr_plain
+    landings against the fixture, under the device rule."""
+    group = "short_lqr_plain"
+    cfg = bc.make_config(PKG, "short")
+    x0s = g[f"{group}_x0"][:2]
+    ctl = bc.make_controller(PKG, "lqr", DYN, g["ol_table"])
+    kind, why = device_gate(ctl)
+    assert kind is not None, why
+    rec, ns, log = _lib.baseline_fly(gpu_ctx, x0s, max_steps=int(cfg.max_time / cfg.dt), dt=cfg.dt, log=False,
+                                     alpha=float(DYN.params.alpha), g=np.asarray(DYN.params.g_vec, float),
+                                     **controller_batch(ctl, kind, x0s))
+    assert log is None
+    assert ns.tolist() == g[f"{group}_nsteps"][:2].tolist() and np.array_equal(rec[:, 1], ns)
+    worst = [0.0]
+    for i in range(2):
+        sx = g[f"{group}_spread_x"][i]
+        check(f"{group}[{i}] final state", rec[i, 4:11], g[f"{group}_final"][i], sx, worst)
+        check(f"{group}[{i}] fuel", rec[i, 2], g[f"{group}_fuel"][i], sx[0], worst)
+
+
 def test_a_wave_where_the_drag_term_is_on_for_some_lanes_only(g):
     """exp_pid_high: at some step speed > 1 holds on some lanes and not on others; every lane's
     whole trajectory meets the rule through that step (the stored lanes) and to the end."""

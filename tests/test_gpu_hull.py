@@ -208,6 +208,30 @@ def test_fused_call_is_query_rule_and_projection(gpu_ctx, order, with_fuel):
     ks.close()
 
 
+def test_fused_call_on_a_set_without_q(gpu_ctx):
+    """A set created without q: the fused call stages no qhull.  The vertex rows and the K rule
+    against the restatement of the search (tests/knn_check.py), the projection certified from
+    lambda alone and held to the restatement's, on two of the trajectory cases."""
+    import knn_check as kc
+    L = _lib()
+    S, _ = hc.trajectory_set()
+    n, K = len(S), 10
+    X = np.stack([x for _, _, x in hc.trajectory_cases(K)[:2]])
+    ks = L.KnnSet(gpu_ctx, S)
+    ks.set_points(S)
+    got = ks.hull(X, X, K, 4, K, 0, 1.0)
+    ks.close()
+    assert got["qhull"] is None
+    idx, _, n_ball, n_feas = kc.knn_query(S, kc.KD, X, K, 1.0)
+    for b in range(2):
+        assert got["k_used"][b] == _host_k_rule(int(n_ball[b]), int(n_feas[b]), K, 4, K, 0) == K
+        assert np.array_equal(got["idx"][b], idx[b])
+        V = S[idx[b]]
+        _valid(got, b, V, X[b], ("no q", b))
+        e = hc.rel_err(got["proj"][b], hc.wolfe(V, X[b])["proj"], V, X[b])
+        assert e <= hc.DEVICE_BOUND, (b, e)
+
+
 def test_constraint_single_calls_are_rows_of_the_batch(gpu_ctx):
     from gp_mpc_rocket_landing_amd.terminal import ConvexHullConstraint
     rng = np.random.default_rng(4)
